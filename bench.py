@@ -23,6 +23,11 @@ roofline.achieved = algorithmic bytes per launch / mean kernel duration, with
 B(src) = 4(V+1) + 8E + V(8 + ceil(deg(src)/8))  (SURVEY.md §8d).
 cpu_baseline = the CPU oracle (C restatement of LinkState::runSpf) on a bounded
 sample of the same sources, rank 0 at N=1 only.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K
+steps and prints the result line. The all-sources line's oracle row check (`check`) and
+`cpu_baseline` take runs of their own and are made with --full only. --dump-outputs DIR
+writes what the last timed step left in the caller's result buffers as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -102,6 +107,45 @@ def token_prefix(row: np.ndarray) -> np.ndarray:
     for _ in range(n):
         k += 1 + int(row[k])
     return row[:k]
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # of .npy payload per rank, under the 64 MB a dump may take
+
+
+def sample_rows(n_rows: int, row_bytes: int) -> np.ndarray:
+    """The rows of an n_rows-row result that a dump keeps: all of them where they fit
+    DUMP_BUDGET_BYTES at `row_bytes` of .npy payload per row, else a fixed (seed 0) sorted
+    sample without replacement. The same arguments give the same rows in every run."""
+    keep = max(1, DUMP_BUDGET_BYTES // max(1, row_bytes))
+    if n_rows <= keep:
+        return np.arange(n_rows, dtype=np.int64)
+    return np.sort(np.random.default_rng(0).choice(n_rows, size=keep, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir: str, arrays: dict, rank: int = 0, world: int = 1) -> None:
+    """--dump-outputs: write each array as <out_dir>/<name>.npy (<name>.rank<r>.npy under
+    --gpus N): bytes as float32, wider integers as float64 (exact below 2^53)."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        a = a.astype(np.float32 if a.dtype.itemsize == 1 else np.float64)
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + (f".rank{rank}" if world > 1 else "") + ".npy"), a)
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes exceed 64 MB"
+
+
+def dump_spf_rows(out_dir, d_dist, d_nh, lo, n_local, rank, world):
+    """The all-sources result of the last step (u64 distances, next-hop bitset bytes) on a
+    fixed sample of the rank's source rows, with the sampled sources' ids."""
+    import torch
+
+    V, nb = int(d_dist.shape[1]), int(d_nh.shape[-1])
+    rows = sample_rows(n_local, V * 8 + V * nb * 4 + 8)
+    idx = torch.from_numpy(rows).to(d_dist.device)
+    dump_outputs(out_dir, {"sources": rows + lo,
+                           "dist": d_dist.index_select(0, idx).cpu().numpy().view(np.uint64),
+                           "next_hops": d_nh.index_select(0, idx).cpu().numpy()}, rank, world)
 
 
 def rows_check(g, d_dist, d_nh, lo: int, n_local: int, use_metric: bool, nrows: int = 8):
@@ -286,6 +330,11 @@ def whatif_main(args):
     units = L * V
     value = units * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and n_links:
+        lrows = sample_rows(n_links, V * 8 + 8)
+        dump_outputs(args.dump_outputs, {"links": lrows + llo,
+                                         "changed": changed.index_select(0, torch.from_numpy(lrows).to(dev)).cpu().numpy()},
+                     rank, world)
     # self-check outside the timed region: every rank's changed rows as a 64-bit digest,
     # all-gathered; rank 0 re-solves a sampled shard (the last rank's links) on its own
     # engine and compares digests, and at N = 1 checks 8 sources x its links against the
@@ -522,6 +571,23 @@ def ksp2_main(args):
     pairs_total = n_src_total * V * args.steps
     value = pairs_total / elapsed
     s_np = srcs.cpu().numpy()
+    if args.dump_outputs and nsrc:
+        # the token rows hold the last block's pairs: a sample of them, with each pair's (src, dst)
+        b_last = ((nsrc - 1) // blk) * blk
+        prows = sample_rows((nsrc - b_last) * V, 2 * tok_cap * 8 + 16)
+        pidx = torch.from_numpy(prows).to(dev)
+
+        def used(tok):  # the engine writes each row's used prefix only: the rest reads as 0
+            rows_ = tok.index_select(0, pidx).cpu().numpy().view(np.uint32)
+            out_ = np.zeros_like(rows_)
+            for i, r in enumerate(rows_):
+                p = token_prefix(r)
+                out_[i, :len(p)] = p
+            return out_
+
+        dump_outputs(args.dump_outputs, {"pair_src": s_np[b_last + prows // V].astype(np.int64),
+                                         "pair_dst": (prows % V), "tokens_k1": used(tok1), "tokens_k2": used(tok2)},
+                     rank, world)
     if world == 1 and not args.no_cpu_baseline:
         # with the CPU leg only: spot check a few pairs against the oracle (outside the
         # timed region; the oracle is the checker, never the measured path)
@@ -677,6 +743,8 @@ def update_main(args):
         step()
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0, dev)
+    if args.dump_outputs:
+        dump_spf_rows(args.dump_outputs, d_dist, d_nh, 0, V, rank, world)
     # the rows must equal a fresh solve of the final (reverted) graph
     chk = torch.empty((2, V), dtype=torch.int64, device=dev)
     eng.solve_device(src.data_ptr(), 2, chk.data_ptr(), 0, nb, use_metric, stream=stream.cuda_stream)
@@ -771,6 +839,8 @@ def adjdb_main(args):
         step(True)
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_spf_rows(args.dump_outputs, d_dist, holder["nh"], 0, V, 0, 1)
     # the graph built from the bytes has the topology's links
     g2 = holder["g2"]
     assert g2.num_nodes == V and g2.num_dir_edges == g.num_dir_edges and g2.num_links == g.num_links
@@ -876,8 +946,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--topology", default="grid100", choices=["grid100", "grid10", "fabric", "wan"])
     ap.add_argument("--no-metric", action="store_true", help="hop-count SPF (useLinkMetric=false)")
+    ap.add_argument("--full", action="store_true",
+                    help="all-sources: also check sampled result rows against the CPU oracle (`check`) and time "
+                         "the CPU baselines (`cpu_baseline`); a run without it only sets up, warms up, times the "
+                         "steps and prints the result line. The other workloads' extra legs keep their own "
+                         "--no-* switches")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step left in the result buffers as "
+                         "DIR/<name>.npy (float32 / float64; a fixed seeded sample of rows where the result is "
+                         "larger than 48 MB)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline leg (all-sources runs it with --full only)")
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--gather", default="compact", choices=["compact", "full"],
                     help="strong scaling exchange: compact = u8/u16 level rows + next hops (uniform-cost graphs), "
@@ -915,6 +994,8 @@ def main():
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     if world_env != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world_env}")
+    if args.dump_outputs and args.workload in ("routes", "decision"):
+        raise SystemExit(f"--dump-outputs: --workload {args.workload} returns route DB tallies, no arrays")
     if args.workload == "whatif":
         return whatif_main(args)
     if args.workload == "ksp2":
@@ -1048,11 +1129,14 @@ def all_sources_main(args):
     kernel_ms = [a.elapsed_time(b) for a, b in evs]
     elapsed = max_over_ranks(elapsed, dev)  # the slowest rank's clock
 
-    # correctness check outside the timed region: a handful of full rows of the last step,
-    # distances AND next-hop bytes, against the CPU oracle (tests' checker) on the same graph
+    if args.dump_outputs and n_local:
+        dump_spf_rows(args.dump_outputs, d_dist, d_nh, lo, n_local, rank, world)
+
+    # correctness check outside the timed region (--full): a handful of full rows of the last
+    # step, distances AND next-hop bytes, against the CPU oracle (tests' checker) on the same graph
     grid_n = {"grid100": 100, "grid10": 10}.get(args.topology)
     check = None
-    if n_local:
+    if n_local and args.full:
         check = rows_check(g, d_dist, d_nh, lo, n_local, use_metric)
 
     gather = None
@@ -1192,7 +1276,7 @@ def all_sources_main(args):
             out["gather"] = gather
         if check is not None:
             out["check"] = check
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(g, args.cpu_seconds, use_metric)
         print(json.dumps(out), flush=True)
     if world > 1:

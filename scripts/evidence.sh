@@ -12,9 +12,9 @@ for W in "$@"; do
   OUT="$R/gpurun_out/$ROUND/ev/$W"
   mkdir -p "$OUT"
   case $W in
-    grid100) ARGS="" ;;
-    fabric)  ARGS="--topology fabric" ;;
-    grid10)  ARGS="--topology grid10" ;;
+    grid100) ARGS="--full" ;;
+    fabric)  ARGS="--full --topology fabric" ;;
+    grid10)  ARGS="--full --topology grid10" ;;
     whatif)  ARGS="--workload whatif --steps 20 --warmup 3" ;;
     update)  ARGS="--workload update --topology fabric --steps 20 --warmup 2" ;;
     ksp2)    ARGS="--workload ksp2 --steps 2 --warmup 1" ;;

@@ -12,6 +12,7 @@ if grep -qiE "illegal memory access|memory access fault|HSA_STATUS_ERROR|hipErro
   echo "GPU fault reported inside the tests; stopping"; exit 3
 fi
 if [ -z "${SKIP_BENCH:-}" ]; then
+  BENCH_ARGS="${BENCH_ARGS:---steps 10 --warmup 2 --full}"  # --full: the oracle row check and the CPU baseline
   timeout -k 10 400 python -u bench.py ${BENCH_ARGS:---steps 10 --warmup 2} > gpurun_out/bench.log 2>&1
   rc=$?; echo "bench rc=$rc"; tail -2 gpurun_out/bench.log; stop_on_fault $rc
 fi

@@ -15,7 +15,7 @@ stop() { case $1 in 0) ;; *) echo "step failed rc=$1; stopping"; exit $1;; esac;
 PMC_AGG=1 PMC_TAG="$TAG/$TOPO/pmc" BENCH_ARGS="--topology $TOPO" bash "$R/scripts/pmc_traffic.sh"; stop $?
 cp "$R/gpurun_out/pmc_$TAG/$TOPO/pmc/pmc_traffic.json" "$OUT/pmc_traffic.json"
 # 2) bench line (default steps/warmup, CPU baseline included)
-cd "$R" && timeout -k 10 300 python3 -u bench.py --topology "$TOPO" --traffic-json "$OUT/pmc_traffic.json" \
+cd "$R" && timeout -k 10 300 python3 -u bench.py --full --topology "$TOPO" --traffic-json "$OUT/pmc_traffic.json" \
   > "$OUT/bench.log" 2>&1; stop $?
 grep '^{' "$OUT/bench.log" | tail -1 > "$OUT/bench.json"; cat "$OUT/bench.json"
 # 3) kernel-trace summary of the same bench command (without the CPU leg)
