@@ -516,11 +516,15 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8))) void
 //    an append slot is base + mbcnt (no wrap mask); a level wider than a half flags the
 //    solve for the u16 full-order re-run of bfs_lvl_kernel, as a deeper-than-253 solve;
 //  * lanes past the frontier read the sentinel row ellv[V] (every slot V, lvl[V] = 0:
-//    never tight), so the pass has no divergent prologue.
+//    never tight), so the pass has no divergent prologue;
+//  * levels of at most 64 nodes run on wave 0 alone, a whole run of them between two
+//    barriers, with a scalar append cursor instead of the shared counter (the narrow run
+//    in the level loop: G100 spends 47 % of its levels there).
 // ---------------------------------------------------------------------------
 struct LeanLayout {
   uint32_t nh, ring, dummy, total;
 };
+constexpr int kLeanProfWords = 11;  // bfs_ell_kernel's OPENR_SPF_PROF counters
 // [0, 32) control, [32, 32 + V + 4) u8 levels, next-hop words, two queue halves, dummies
 __host__ __device__ inline LeanLayout lean_layout(uint32_t V, uint32_t nh_words, uint32_t ring_cap) {
   LeanLayout l;
@@ -555,7 +559,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform (scalar loop bounds)
   const uint32_t nh_words = N::words(V);
   const LeanLayout lay = lean_layout(V, nh_words, ring_cap);
-  lds_u32* const ctl = (lds_u32*)(size_t)0u;  // [0..3] append counters, [4] overflow flag, [7] next unit
+  lds_u32* const ctl = (lds_u32*)(size_t)0u;  // [0..3] append counters, [4] overflow flag, [5, 6] narrow-run hand-back, [7] next unit
   lds_u8* const lvl = (lds_u8*)(size_t)32u;
   lds_u32* const lvl_w = (lds_u32*)(size_t)32u;
   lds_u32* const nh = (lds_u32*)(size_t)lay.nh;
@@ -568,12 +572,15 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
   const uint32_t half = ring_cap / 2u;
   const uint32_t count = a.perm ? a.part[a.cls] : a.n, first = a.perm ? a.part[kMaxClasses + a.cls] : 0u;
   *my_dummy = 0xFFFFFFFFu;  // only ever ORed afterwards: its fields are never zero
-  // tuning (OPENR_SPF_PROF): wave 0's cycles per phase of its first pass of every
+  // tuning (OPENR_SPF_PROF): wave 0's cycles per phase of its first pass of every wide
   // level: [0] barrier -> queue entry, [1] ELL row load, [2] level / set reads, [3] atomics,
-  // [4] append, [5] drain + barrier, [6] levels, [7] solves. A stamp follows an asm use of
-  // the value the phase waits for, so it is taken once that value has arrived.
+  // [4] append, [5] drain + barrier; [6] cycles of the narrow runs (hand-back barrier and
+  // reload included). A stamp follows an asm use of the value the phase waits for, so it is
+  // taken once that value has arrived. Counts (prof[7 ..]): [0] levels, wide and narrow,
+  // [1] solves, [2] narrow levels, [3] narrow runs.
   const bool pf = PROF && prof != nullptr && wave == 0;
-  unsigned long long pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long pacc[7] = {0, 0, 0, 0, 0, 0, 0};
+  uint32_t pcnt[4] = {0, 0, 0, 0};
   long long ts = 0;
 #define OPENR_LEAN_STAMP(i, dep)                             \
   do {                                                       \
@@ -625,111 +632,184 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
       bool overflow = false;  // block-uniform
       if (pf) {
         ts = (long long)__builtin_amdgcn_s_memtime();
-        pacc[7] += 1;
+        pcnt[1] += 1;
       }
       // one lane per frontier node, its K = 4 ELL slots; NPP nodes per wave pass
       // (4 lanes per node, one slot each, measured no faster on strong-scaling shards:
       // the level then waits for every wave's shorter chain at the barrier instead)
       constexpr uint32_t K = 4u, NPP = 64u, NPB = (uint32_t)BLOCK;
       const uint32_t lnode = lane;
+      // One pass of level lev for the lane's frontier node u (past the level: the sentinel
+      // row): row, nh(u), the four level reads together, then the four atomics, then the
+      // ballots of the first arrivals. `st`: stamp the phases.
+      struct Pass {
+        uint32_t vv[K], off[K + 1];
+        unsigned long long bj[K];
+        bool fresh[K];
+      };
+      auto expand = [&](uint32_t u, bool live, uint32_t lev, bool st, Pass& p) __attribute__((always_inline)) {
+        if constexpr (DELTA) {
+          const uint32_t d4 = g.elld[live ? u : 0u];
+          const uint32_t dd = live ? d4 : 0u;  // past the level: every slot is the sentinel V
+#pragma unroll
+          for (uint32_t j = 0; j < K; ++j) p.vv[j] = u + (uint32_t)__builtin_amdgcn_sbfe((int32_t)dd, 8u * j, 8u);
+        } else {
+          const uint4 ell = g.ellv[u];  // ellv[V] = sentinel row
+          p.vv[0] = ell.x;
+          p.vv[1] = ell.y;
+          p.vv[2] = ell.z;
+          p.vv[3] = ell.w;
+        }
+        if (st) OPENR_LEAN_STAMP(1, p.vv[0]);
+        const uint32_t x = __builtin_amdgcn_ubfe(nh[u >> kLog], u << kShl, kBits);  // final since lev-1
+        // the level reads issue together, then the atomics
+        uint32_t lv[K], old[K];
+#pragma unroll
+        for (uint32_t j = 0; j < K; ++j) lv[j] = lvl[p.vv[j]];
+        if (st) OPENR_LEAN_STAMP(2, lv[0] + x);
+#pragma unroll
+        for (uint32_t j = 0; j < K; ++j) {
+          const uint32_t v = p.vv[j];
+          const bool tight = lv[j] > lev;  // first or equal-cost arrival (LinkState.cpp:857-873)
+          old[j] = lds_or(tight ? &nh[v >> kLog] : my_dummy, x << ((v << kShl) & 31u));
+        }
+        __builtin_amdgcn_sched_barrier(0);  // all atomics in flight before their results are used
+        if (st) OPENR_LEAN_STAMP(3, old[0]);
+        p.off[0] = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < K; ++j) {
+          // v's field was empty: this is the first arrival (a dummy field never is)
+          p.fresh[j] = __builtin_amdgcn_ubfe(old[j], p.vv[j] << kShl, kBits) == 0u;
+          p.bj[j] = __builtin_amdgcn_ballot_w64(p.fresh[j]);
+          p.off[j + 1] = p.off[j] + (uint32_t)__popcll(p.bj[j]);
+        }
+      };
+      // The pass's first arrivals go to queue entries at, at + 1, ... (slot order, then lane
+      // order) and get their level. Only the appending arrival stores v's level; another
+      // arrival of this level that reads it earlier sees "unset" (> L), i.e. tight, as it is.
+      auto append = [&](const Pass& p, uint32_t at, uint8_t lnext) __attribute__((always_inline)) {
+#pragma unroll
+        for (uint32_t j = 0; j < K; ++j) {
+          if (p.fresh[j]) {
+            const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(p.bj[j] >> 32),
+                                                            __builtin_amdgcn_mbcnt_lo((uint32_t)p.bj[j], 0u));
+            ring[at + p.off[j] + slot] = (uint16_t)p.vv[j];
+            lvl[p.vv[j]] = lnext;
+          }
+        }
+      };
       uint32_t q = ring[half + wave * NPP + lnode];  // first pass's queue entry of level 1
       while (cur) {
         if (L + 1u >= 0xFFu) {  // next level not representable in u8
           overflow = true;
           break;
         }
-        // level L: entries [0, cur) of half L & 1; level L+1 appends to the other half,
-        // counted in ctl[(L + 1) & 3] (zeroed here: last read three barriers ago); bit 31
-        // of that count flags a level that outgrew its half
+        // level L: entries [0, cur) of half L & 1; level L+1 appends to the other half
+        const bool narrow = cur <= NPP;  // block-uniform: cur was read after a barrier
         lds_u32* const cnt = &ctl[(L + 1u) & 3u];
-        if (tid == 0) ctl[(L + 2u) & 3u] = 0;
         const uint32_t rd = (L & 1u) * half, wr = half - rd;
-        const uint8_t lnext = (uint8_t)(L + 1u);
-        for (uint32_t fb = wave * NPP; fb < cur; fb += NPB) {
-          const uint32_t idx = fb + lnode;
-          if (fb != wave * NPP) q = ring[rd + idx];  // the first pass's entry was read with the count
-          const uint32_t u = idx < cur ? q : V;  // past the level: the sentinel row
-          const bool st = pf && fb == 0u;        // stamps: wave 0's first pass of the level
-          if (st) OPENR_LEAN_STAMP(0, u);
-          uint32_t vv[K];
-          if constexpr (DELTA) {
-            const bool live = idx < cur;
-            const uint32_t d4 = g.elld[live ? u : 0u];
-            const uint32_t dd = live ? d4 : 0u;  // past the level: every slot is the sentinel V
-#pragma unroll
-            for (uint32_t j = 0; j < K; ++j) vv[j] = u + (uint32_t)__builtin_amdgcn_sbfe((int32_t)dd, 8u * j, 8u);
-          } else {
-            const uint4 ell = g.ellv[u];  // ellv[V] = sentinel row
-            vv[0] = ell.x;
-            vv[1] = ell.y;
-            vv[2] = ell.z;
-            vv[3] = ell.w;
-          }
-          if (st) OPENR_LEAN_STAMP(1, vv[0]);
-          const uint32_t x = __builtin_amdgcn_ubfe(nh[u >> kLog], u << kShl, kBits);  // final since L-1
-          // the level reads issue together, then the atomics
-          uint32_t lv[K], old[K];
-#pragma unroll
-          for (uint32_t j = 0; j < K; ++j) lv[j] = lvl[vv[j]];
-          if (st) OPENR_LEAN_STAMP(2, lv[0] + x);
-#pragma unroll
-          for (uint32_t j = 0; j < K; ++j) {
-            const uint32_t v = vv[j];
-            const bool tight = lv[j] > L;  // first or equal-cost arrival (LinkState.cpp:857-873)
-            old[j] = lds_or(tight ? &nh[v >> kLog] : my_dummy, x << ((v << kShl) & 31u));
-          }
-          __builtin_amdgcn_sched_barrier(0);  // all atomics in flight before their results are used
-          if (st) OPENR_LEAN_STAMP(3, old[0]);
-          unsigned long long bj[K];
-          bool fresh[K];
-          uint32_t off[K + 1];
-          off[0] = 0;
-#pragma unroll
-          for (uint32_t j = 0; j < K; ++j) {
-            // v's field was empty: this is the first arrival (a dummy field never is)
-            fresh[j] = __builtin_amdgcn_ubfe(old[j], vv[j] << kShl, kBits) == 0u;
-            bj[j] = __builtin_amdgcn_ballot_w64(fresh[j]);
-            off[j + 1] = off[j] + (uint32_t)__popcll(bj[j]);
-          }
-          const uint32_t total = off[K];
-          if (total) {  // wave-uniform
-            const uint32_t leader = (uint32_t)__builtin_amdgcn_readfirstlane(lane);
-            uint32_t wbase = 0;
-            if (lane == leader) wbase = lds_add(cnt, total);
-            const uint32_t bse = __builtin_amdgcn_readfirstlane(wbase);
-            if (bse + total <= half) {  // wave-uniform: the level fits its half so far
-#pragma unroll
-              for (uint32_t j = 0; j < K; ++j) {
-                if (fresh[j]) {
-                  const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(bj[j] >> 32),
-                                                                  __builtin_amdgcn_mbcnt_lo((uint32_t)bj[j], 0u));
-                  ring[wr + bse + off[j] + slot] = (uint16_t)vv[j];
-                  // only the appending arrival stores v's level; another arrival of this
-                  // level that reads it earlier sees "unset" (> L), i.e. tight, as it is
-                  lvl[vv[j]] = lnext;
-                }
+        if (narrow) {
+          // Narrow run: a level of at most NPP nodes is one pass of one wave, so wave 0 alone
+          // expands it and every following level for as long as the count stays in
+          // [1, NPP], while the other waves wait at the barrier below. No shared counter and
+          // no barrier inside the run: the append cursor is the pass's own count (a scalar),
+          // and a wave's LDS operations complete in issue order, so the next level's queue
+          // entries are read straight after the stores (as bfs_wave_kernel does). The run
+          // ends on the loop's own exits (count 0, every node reached, depth, a level wider
+          // than its half) or on a count above NPP, and hands the state back in ctl[5], ctl[6].
+          if (wave == 0) {
+            for (;;) {
+              const bool live = lnode < cur;
+              Pass p;
+              expand(live ? q : V, live, L, false, p);
+              const uint32_t total = p.off[K];
+              if (total > half) {  // the level outgrows its half
+                cur = 0x80000000u;
+                break;
               }
-            } else if (lane == leader) {
-              lds_or(cnt, 0x80000000u);  // the level outgrows its half
+              append(p, ((L + 1u) & 1u) * half, (uint8_t)(L + 1u));
+              ++L;
+              cur = total;
+              reached += total;
+              q = ring[(L & 1u) * half + lnode];  // level L's entries, as just stored
+              if (pf) {
+                pcnt[0] += 1;
+                pcnt[2] += 1;
+              }
+              if (cur - 1u >= NPP || reached == V || L + 1u >= 0xFFu) break;
             }
+            // Hand-back, stored by every lane of the wave (the same words: no per-lane
+            // branch whose join would make cur, L and reached look divergent to the compiler).
+            ctl[5] = cur;                 // bit 31: overflow, as the shared count carries it
+            ctl[6] = L | (reached << 8);  // L <= 0xFF, reached <= V < 2^16
+            // The counter level L appends to if it is wide (the wide path zeroes it a level
+            // ahead). Its last readers took a count from it as their first instruction after
+            // an earlier barrier and held the value before they reached the barrier below
+            // (readfirstlane waits for it). The latest such read is the one that started this
+            // run, and the word is that read's only when the run is 3, 7, ... levels long:
+            // at least three levels of dependent LDS round trips lie between the two.
+            ctl[(L + 1u) & 3u] = 0;
           }
-          if (st) OPENR_LEAN_STAMP(4, total);
+        } else {
+          // two-wave level: appends counted in ctl[(L + 1) & 3] (the next one is zeroed here:
+          // last read three barriers ago); bit 31 of that count flags a level that outgrew
+          // its half
+          if (tid == 0) ctl[(L + 2u) & 3u] = 0;
+          const uint8_t lnext = (uint8_t)(L + 1u);
+          for (uint32_t fb = wave * NPP; fb < cur; fb += NPB) {
+            const uint32_t idx = fb + lnode;
+            if (fb != wave * NPP) q = ring[rd + idx];  // the first pass's entry was read with the count
+            const bool live = idx < cur;
+            const uint32_t u = live ? q : V;  // past the level: the sentinel row
+            const bool st = pf && fb == 0u;   // stamps: wave 0's first pass of the level
+            if (st) OPENR_LEAN_STAMP(0, u);
+            Pass p;
+            expand(u, live, L, st, p);
+            const uint32_t total = p.off[K];
+            if (total) {  // wave-uniform
+              const uint32_t leader = (uint32_t)__builtin_amdgcn_readfirstlane(lane);
+              uint32_t wbase = 0;
+              if (lane == leader) wbase = lds_add(cnt, total);
+              const uint32_t bse = __builtin_amdgcn_readfirstlane(wbase);
+              if (bse + total <= half) {  // wave-uniform: the level fits its half so far
+                append(p, wr + bse, lnext);
+              } else if (lane == leader) {
+                lds_or(cnt, 0x80000000u);  // the level outgrows its half
+              }
+            }
+            if (st) OPENR_LEAN_STAMP(4, total);
+          }
         }
-        lds_barrier();
-        // the next level's count and its first pass's queue entry, read together
-        const uint32_t c = __builtin_amdgcn_readfirstlane(*cnt);
-        q = ring[wr + wave * NPP + lnode];
-        if (pf) {
-          OPENR_LEAN_STAMP(5, c);
-          pacc[6] += 1;
+        lds_barrier();  // the one barrier of a wide level and of a whole narrow run
+        // the next level's count (after a narrow run: the count wave 0 left) and its first
+        // pass's queue entry, read together (volatile: the compiler otherwise moves the
+        // entry's read to the top of the next level, behind the count's round trip)
+        const uint32_t c = __builtin_amdgcn_readfirstlane(*(narrow ? &ctl[5] : cnt));
+        q = *(volatile lds_u16*)&ring[wr + wave * NPP + lnode];
+        if (narrow) {
+          // the rest of the state wave 0 left: L and reached (the count of level L included);
+          // the queue entry again, from the half of that L
+          const uint32_t s = __builtin_amdgcn_readfirstlane(ctl[6]);
+          L = s & 0xFFu;
+          reached = s >> 8;
+          q = ring[(L & 1u) * half + wave * NPP + lnode];
+          if (pf) {
+            OPENR_LEAN_STAMP(6, q);
+            pcnt[3] += 1;
+          }
+        } else {
+          if (pf) {
+            OPENR_LEAN_STAMP(5, c);
+            pcnt[0] += 1;
+          }
+          ++L;
+          reached += c;
         }
-        ++L;
         if (c >> 31) {  // uniform after the barrier
           overflow = true;
           break;
         }
         cur = c;
-        reached += cur;
         if (reached == V) break;  // every node reached: the newest level cannot expand tightly
       }
       if (overflow) {
@@ -744,8 +824,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     unit = ctl[7];
   }
 #undef OPENR_LEAN_STAMP
-  if (pf && lane == 0)
-    for (int i = 0; i < 8; ++i) atomicAdd(&prof[i], pacc[i]);
+  if (pf && lane == 0) {
+    for (int i = 0; i < 7; ++i) atomicAdd(&prof[i], pacc[i]);
+    for (int i = 0; i < 4; ++i) atomicAdd(&prof[7 + i], (unsigned long long)pcnt[i]);
+  }
   retire_workgroup(ctr, nullptr);
 }
 
@@ -823,7 +905,7 @@ hipError_t launch_lvl_lean(const DevGraph& g, const SolveArgs& a, uint64_t cost,
   // OPENR_SPF_LEAN_DELTA=0: 16-byte ellv rows even when the delta rows exist
   const bool delta = g.elld && env_u32("OPENR_SPF_LEAN_DELTA", 1u, 0u, 1u) != 0;
   // registers for 5 waves per SIMD, the occupancy LDS allows G100 (10 workgroups of 2 waves
-  // per CU): 89 VGPRs, no scratch, 31 SGPR spills; a target of 8 spilled 21 VGPRs to
+  // per CU): 90 VGPRs, no scratch, 33 SGPR spills; a target of 8 spilled 21 VGPRs to
   // scratch and 50 SGPRs (r06, interleaved A/B: 0.707 vs 0.715 ms median)
   auto k = want_prof ? (delta ? bfs_ell_kernel<MODE, BLOCK, true, true, 5> : bfs_ell_kernel<MODE, BLOCK, true, false, 5>)
                      : (delta ? bfs_ell_kernel<MODE, BLOCK, false, true, 5> : bfs_ell_kernel<MODE, BLOCK, false, false, 5>);
@@ -839,22 +921,26 @@ hipError_t launch_lvl_lean(const DevGraph& g, const SolveArgs& a, uint64_t cost,
   static unsigned long long* prof_buf = nullptr;
   unsigned long long* prof = nullptr;
   if (want_prof) {
-    if (!prof_buf && hipMalloc(&prof_buf, 8 * sizeof(unsigned long long)) != hipSuccess) prof_buf = nullptr;
+    if (!prof_buf && hipMalloc(&prof_buf, kLeanProfWords * sizeof(unsigned long long)) != hipSuccess) prof_buf = nullptr;
     prof = prof_buf;
-    if (prof) (void)hipMemsetAsync(prof, 0, 8 * sizeof(unsigned long long), s);
+    if (prof) (void)hipMemsetAsync(prof, 0, kLeanProfWords * sizeof(unsigned long long), s);
   }
   note_launch("bfs_ell_kernel");
   hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), lds, s, g, a, cost, ring_cap, ctr, ovf_count, nt_stores(), prof);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && prof) {
-    unsigned long long h[8];
+    unsigned long long h[kLeanProfWords];
     if (hipMemcpyAsync(h, prof, sizeof(h), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess) {
-      const double lv = h[6] ? (double)h[6] : 1.0;
+      // h[0..5] wide-level phase cycles, h[6] narrow-run cycles, then the counts
+      const unsigned long long levels = h[7], solves = h[8], nlevels = h[9], nruns = h[10];
+      const double sv = solves ? (double)solves : 1.0, nl = nlevels ? (double)nlevels : 1.0;
+      const double wl = levels > nlevels ? (double)(levels - nlevels) : 1.0;  // wide levels
       std::fprintf(stderr,
-                   "bfs_ell: block=%d grid=%u n=%u solves=%llu levels/solve=%.1f | cycles/level: entry %.0f row %.0f "
-                   "reads %.0f atomics %.0f append %.0f barrier %.0f\n",
-                   BLOCK, grid, a.n, h[7], h[7] ? lv / (double)h[7] : 0.0, h[0] / lv, h[1] / lv, h[2] / lv, h[3] / lv,
-                   h[4] / lv, h[5] / lv);
+                   "bfs_ell: block=%d grid=%u n=%u solves=%llu levels/solve=%.1f | cycles/level (wide levels only): "
+                   "entry %.0f row %.0f reads %.0f atomics %.0f append %.0f barrier %.0f | narrow levels/solve=%.1f "
+                   "cycles/narrow level %.0f narrow runs/solve=%.1f\n",
+                   BLOCK, grid, a.n, solves, (double)levels / sv, h[0] / wl, h[1] / wl, h[2] / wl, h[3] / wl, h[4] / wl,
+                   h[5] / wl, (double)nlevels / sv, h[6] / nl, (double)nruns / sv);
     }
   }
   return e;
