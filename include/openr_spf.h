@@ -22,6 +22,8 @@
  *                              for every (link, source), reduced to changed-node counts
  *   openr_spf_whatif_delta     the same sweep plus each unit's changed nodes with their
  *                              new distance and next-hop bits
+ *   openr_spf_whatif_sets      the sweep with a set of links per unit (node failures,
+ *                              shared-risk link groups); _sets_delta adds the delta
  *   openr_spf_ksp2             LinkState::getKthPaths(src, dst, 1 and 2) (LinkState.cpp:762-791)
  *                              for a batch of pairs, paths traced on the device
  *   openr_spf_patch_graph      attribute-only mirror updates (metric, Link::isUp, node
@@ -260,6 +262,57 @@ int openr_spf_whatif_delta_device(openr_spf_ctx* ctx, int device_index, const ui
                                   uint32_t* d_node, uint64_t* d_dist, uint8_t* d_nh, uint64_t cap,
                                   uint32_t nh_bytes, void* stream, uint64_t* out_total,
                                   uint64_t* out_solved);
+
+/* What-if sweep over link sets: node failures (all of a router's links at once) and
+   shared-risk link groups (the links that share a fibre, a line card, a conduit). The
+   failure unit is a set of links instead of one link; everything else is the single-link
+   sweep. Sets are a CSR: set i = set_links[set_ptr[i] .. set_ptr[i + 1]). Unit (i, j) is
+   LinkState::runSpf(sources[j], useLinkMetric, set i) (LinkState.cpp:808-882, the set
+   passed as the linksToIgnore argument) compared with the no-failure SPF of sources[j].
+   changed [n_sets][n_sources] and *out_solved mean what they mean for openr_spf_whatif.
+   An empty set changes nothing; a link listed twice in a set counts once. A unit is
+   affected iff some link of its set carries a tight edge of the base SPF in either
+   direction (nh and dist depend on tight edges only, so any other set changes nothing:
+   0 without a solve); on exact-order plans with zero or wrapped metrics, iff some link of
+   its set is a link of the graph. *out_solved = base solves + affected units, also added
+   to stats.spf_runs. Every affected unit is re-solved with its set ignored (seeded from
+   the base rows where the rounds kernel runs). A call whose sets are all singletons
+   returns what openr_spf_whatif returns for those links.
+   A link id >= num_links, or a set_ptr that does not ascend, is OPENR_SPF_EINVAL. Sets
+   are split in contiguous blocks across the context's devices. */
+int openr_spf_whatif_sets(openr_spf_ctx* ctx, const uint32_t* set_ptr, const uint32_t* set_links,
+                          uint32_t n_sets, const uint32_t* sources, uint32_t n_sources,
+                          uint32_t flags, uint32_t* changed, uint64_t* out_solved);
+
+/* Device-buffer form (d_set_ptr [n_sets + 1], d_set_links [n_set_links], d_changed
+   [n_sets][n_sources]; all device memory). Link ids >= L are ignored, as the ignore sets
+   of openr_spf_solve_device are; no slice is read past n_set_links. Synchronizes `stream`
+   once (the affected-unit count sizes the chunked solves). */
+int openr_spf_whatif_sets_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_set_ptr,
+                                 const uint32_t* d_set_links, uint32_t n_sets,
+                                 uint32_t n_set_links, const uint32_t* d_sources,
+                                 uint32_t n_sources, uint32_t flags, uint32_t* d_changed,
+                                 void* stream, uint64_t* out_solved);
+
+/* Link-set sweep with the per-unit delta: openr_spf_whatif_delta with unit i a set. ptr,
+   node, dist, nh, cap, OPENR_SPF_E2BIG and *out_solved mean exactly what they mean there;
+   delta->ptr has n_sets * n_sources + 1 entries and each unit's nodes are ascending. */
+int openr_spf_whatif_sets_delta(openr_spf_ctx* ctx, const uint32_t* set_ptr,
+                                const uint32_t* set_links, uint32_t n_sets,
+                                const uint32_t* sources, uint32_t n_sources, uint32_t flags,
+                                uint32_t* changed, openr_spf_whatif_delta_t* delta,
+                                uint64_t* out_solved);
+
+/* Device-buffer form: openr_spf_whatif_delta_device with unit i a set. Each unit's entries
+   are in the order the re-solve found them (not sorted). Synchronizes `stream`. */
+int openr_spf_whatif_sets_delta_device(openr_spf_ctx* ctx, int device_index,
+                                       const uint32_t* d_set_ptr, const uint32_t* d_set_links,
+                                       uint32_t n_sets, uint32_t n_set_links,
+                                       const uint32_t* d_sources, uint32_t n_sources,
+                                       uint32_t flags, uint32_t* d_changed, uint64_t* d_ptr,
+                                       uint32_t* d_node, uint64_t* d_dist, uint8_t* d_nh,
+                                       uint64_t cap, uint32_t nh_bytes, void* stream,
+                                       uint64_t* out_total, uint64_t* out_solved);
 
 /* LinkState::getKthPaths(src[i], dst[i], 1) and (.., 2) (LinkState.cpp:762-791, with
    traceOnePath :398-419) for a batch of pairs, traced on the device. Per pair, tok1 /

@@ -88,6 +88,7 @@ struct Device {
   DevBuf<uint64_t> base_dist, base_tight, wdist;
   DevBuf<uint8_t> base_nh, wnh;
   DevBuf<uint32_t> wsrc, wlink, wunit, wcount, wiota, win_links, win_src, wchanged;
+  DevBuf<uint32_t> wbeg, wend, win_ptr;  // link-set sweep: each listed unit's slice of the set CSR; host form's set_ptr
   DevBuf<uint32_t> wchanged_t;  // grouped repair: results source-major, transposed into the caller's rows
   DevBuf<uint16_t> base_tin;  // what-if base SPF: tight in-degree rows (rounds plan)
   size_t wiota_n = 0;  // wiota[0, wiota_n) holds 0, 1, 2, ... (kept across calls)
@@ -530,24 +531,70 @@ hipError_t ensure_iota(Device& d, size_t n, hipStream_t s) {
 // Bytes of chunk result rows a what-if sweep may hold on a device at once.
 constexpr size_t kWhatifChunkBytes = size_t(1) << 30;
 
-// Per-link-failure what-if sweep on one device (spf_sweep.hip has the unit semantics):
-// base SPF with tight edges -> filter of the affected units -> chunks of single-link
-// ignore-set solves through the ordinary launcher -> row comparison against the base.
-// Reads the affected-unit count back (one stream sync) to size the chunks.
-hipError_t whatif_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, const Plan& ign_plan,
-                            const uint32_t* d_links, uint32_t n_links, const uint32_t* d_sources, uint32_t n_src,
-                            uint32_t* d_changed, hipStream_t s, uint32_t* solved, bool use_link_metric,
-                            const WhatifDelta& dl = WhatifDelta{}) {
-  const uint32_t V = ctx->V, tw = (ctx->E + 63u) / 64u;
-  const uint32_t nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
-  *solved = 0;
-  if (!n_src || !n_links) return hipSuccess;
-  hipError_t err;
 #define OPENR_TRY(x)              \
   do {                            \
     err = (x);                    \
     if (err != hipSuccess) return err; \
   } while (0)
+
+// OPENR_SPF_PROF tuning aid: the phase split of `nres` seeded re-solves (SolveArgs::prof_solve:
+// ten u64 per solve, 100 MHz wall clock) and how many ran side by side.
+void print_resolve_prof(const std::vector<unsigned long long>& h, uint32_t nres) {
+  if (!nres) return;
+  unsigned long long t0 = ~0ull, t1 = 0;
+  double ph[7] = {0}, na = 0, rd = 0, rk = 0, tot = 0;
+  for (uint32_t k = 0; k < nres; ++k) {
+    const unsigned long long* x = &h[10 * (size_t)k];
+    t0 = std::min(t0, x[0]);
+    t1 = std::max(t1, x[7]);
+    for (int q = 0; q < 7; ++q) ph[q] += (double)(x[q + 1] - x[q]) / 100.0;
+    tot += (double)(x[7] - x[0]) / 100.0;
+    na += (double)x[8];
+    rd += (double)(x[9] & 0xFFFFFFFFull);
+    rk += (double)(x[9] >> 32);
+  }
+  std::fprintf(stderr,
+               "[whatif resolve] n=%u span=%.1fus mean solve %.1fus: seed-a %.1f seed-A %.1f seed-c %.1f "
+               "dist %.1f indeg %.1f kahn %.1f compare %.1f | |A| %.1f, rounds: A+c+dist %.1f, kahn %.1f, "
+               "concurrency %.0f\n",
+               nres, (t1 - t0) / 100.0, tot / nres, ph[0] / nres, ph[1] / nres, ph[2] / nres, ph[3] / nres,
+               ph[4] / nres, ph[5] / nres, ph[6] / nres, na / nres, rd / nres, rk / nres,
+               tot / ((t1 - t0) / 100.0));
+  // duration spread, its correlation with |A|, and the solves running over the span
+  std::vector<double> dur(nres), asz(nres);
+  for (uint32_t k = 0; k < nres; ++k) {
+    dur[k] = (double)(h[10 * (size_t)k + 7] - h[10 * (size_t)k]) / 100.0;
+    asz[k] = (double)h[10 * (size_t)k + 8];
+  }
+  std::vector<double> srt = dur;
+  std::sort(srt.begin(), srt.end());
+  const double md = tot / nres, ma = na / nres;
+  double sxy = 0, sxx = 0, syy = 0;
+  for (uint32_t k = 0; k < nres; ++k) {
+    sxy += (dur[k] - md) * (asz[k] - ma);
+    sxx += (dur[k] - md) * (dur[k] - md);
+    syy += (asz[k] - ma) * (asz[k] - ma);
+  }
+  std::fprintf(stderr, "  duration p10 %.1f p50 %.1f p90 %.1f max %.1f us; corr(duration, |A|) %.2f; running at",
+               srt[nres / 10], srt[nres / 2], srt[nres * 9 / 10], srt.back(),
+               sxx > 0 && syy > 0 ? sxy / std::sqrt(sxx * syy) : 0.0);
+  for (int q : {10, 25, 50, 75, 90, 95}) {
+    const unsigned long long tq = t0 + (t1 - t0) * q / 100;
+    uint32_t live = 0;
+    for (uint32_t k = 0; k < nres; ++k) live += (h[10 * (size_t)k] <= tq && h[10 * (size_t)k + 7] > tq) ? 1u : 0u;
+    std::fprintf(stderr, " %d%%:%u", q, live);
+  }
+  std::fprintf(stderr, "\n");
+}
+
+// Base SPF of a what-if sweep (single links or link sets): every source's no-failure rows
+// into d.base_dist / base_nh / base_tight, and on the rounds plan each row's tight
+// in-degrees into d.base_tin for the seeded re-solves (*base_tin says whether).
+hipError_t whatif_base_solve(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, const uint32_t* d_sources,
+                             uint32_t n_src, hipStream_t s, bool* base_tin) {
+  const uint32_t V = ctx->V, tw = (ctx->E + 63u) / 64u;
+  const uint32_t nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
+  hipError_t err;
   OPENR_TRY(d.base_dist.reserve((size_t)n_src * V));
   OPENR_TRY(d.base_nh.reserve((size_t)n_src * V * nb));
   OPENR_TRY(d.base_tight.reserve((size_t)n_src * tw));
@@ -564,55 +611,106 @@ hipError_t whatif_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan
   a.ovf_list = d.ovf.p;
   a.work = d.work.p;
   // the rounds kernel also leaves each base row's tight in-degrees for the seeded re-solves
-  const bool base_tin = base_plan.rounds && !base_plan.exact && !base_plan.bfs;
-  if (base_tin) {
+  *base_tin = base_plan.rounds && !base_plan.exact && !base_plan.bfs;
+  if (*base_tin) {
     OPENR_TRY(d.base_tin.reserve((size_t)n_src * V));
     a.tin_out = d.base_tin.p;
   }
-  OPENR_TRY(launch(ctx, d, base_plan, a, s));
-  // re-solve the `count` units listed in wsrc / wlink / wunit (ignore set = the unit's
-  // link) and compare each row with its source's base row
-  auto resolve_units = [&](uint32_t count, uint32_t base) -> hipError_t {
-    hipError_t e2;
-    const size_t row = (size_t)V * (8u + nb);
-    const uint32_t chunk = (uint32_t)std::min<size_t>(count, std::max<size_t>(1, kWhatifChunkBytes / row));
-    if ((e2 = d.wdist.reserve((size_t)chunk * V)) != hipSuccess) return e2;
-    if ((e2 = d.wnh.reserve((size_t)chunk * V * nb)) != hipSuccess) return e2;
-    if ((e2 = ensure_iota(d, (size_t)chunk + 1u, s)) != hipSuccess) return e2;
-    if ((e2 = d.ovf.reserve((size_t)chunk * ctx->nsl_max())) != hipSuccess) return e2;
-    for (uint32_t off0 = 0; off0 < count; off0 += chunk) {
-      const uint32_t m = std::min(chunk, count - off0), off = base + off0;
-      SolveArgs b{};
-      b.sources = d.wsrc.p + off;
-      b.n = m;
+  return launch(ctx, d, base_plan, a, s);
+}
+
+// Re-solve the `count` units listed from `base` on in wsrc / wunit and compare each row with
+// its source's base row. set_links == nullptr: unit k ignores the single link wlink[k];
+// else it ignores set_links[wbeg[k], wend[k]) (link sets: the list points into the caller's
+// CSR, nothing is copied).
+hipError_t whatif_resolve_units(openr_spf_ctx* ctx, Device& d, const Plan& ign_plan, uint32_t count, uint32_t base,
+                                const uint32_t* set_links, uint32_t n_src, bool base_tin, uint32_t* d_changed,
+                                const WhatifDelta& dl, hipStream_t s) {
+  const uint32_t V = ctx->V;
+  const uint32_t nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
+  hipError_t e2;
+  const size_t row = (size_t)V * (8u + nb);
+  const uint32_t chunk = (uint32_t)std::min<size_t>(count, std::max<size_t>(1, kWhatifChunkBytes / row));
+  if ((e2 = d.wdist.reserve((size_t)chunk * V)) != hipSuccess) return e2;
+  if ((e2 = d.wnh.reserve((size_t)chunk * V * nb)) != hipSuccess) return e2;
+  if (!set_links && (e2 = ensure_iota(d, (size_t)chunk + 1u, s)) != hipSuccess) return e2;
+  if ((e2 = d.ovf.reserve((size_t)chunk * ctx->nsl_max())) != hipSuccess) return e2;
+  std::vector<unsigned long long> prof_rec;
+  for (uint32_t off0 = 0; off0 < count; off0 += chunk) {
+    const uint32_t m = std::min(chunk, count - off0), off = base + off0;
+    SolveArgs b{};
+    b.sources = d.wsrc.p + off;
+    b.n = m;
+    if (set_links) {  // solve k ignores set_links[wbeg[off + k], wend[off + k])
+      b.ign_ptr = d.wbeg.p + off;
+      b.ign_end = d.wend.p + off;
+      b.ign_links = set_links;
+    } else {
       b.ign_ptr = d.wiota.p;  // solve k ignores exactly wlink[off + k]
       b.ign_links = d.wlink.p + off;
-      b.dist = d.wdist.p;
-      b.nh = d.wnh.p;
-      b.nh_bytes = nb;
-      b.nh_bits = ctx->nh_bits;
-      b.ovf_list = d.ovf.p;
-      b.work = d.work.p;
-      // the rounds kernel starts each unit from its source's base rows (only the nodes the
-      // failed link pushes back are re-solved); other kernels solve from scratch
-      b.seed_dist = d.base_dist.p;
-      b.seed_tight = d.base_tight.p;
-      b.seed_unit = d.wunit.p + off;
-      b.seed_nsrc = n_src;
-      b.seed_tin = base_tin ? d.base_tin.p : nullptr;
-      // ... and compares each solve with the base rows itself (no rows through HBM)
-      const bool fused = ign_plan.rounds && !ign_plan.exact && !ign_plan.bfs;
-      if (fused) {
-        b.seed_nh = d.base_nh.p;
-        b.seed_changed = d_changed;
-        b.delta = dl;
-      }
-      if ((e2 = launch(ctx, d, ign_plan, b, s)) != hipSuccess) return e2;
-      if (!fused && (e2 = launch_rows_compare(m, V, nb, d.wdist.p, d.wnh.p, d.base_dist.p, d.base_nh.p, d.wunit.p + off, n_src,
-                                    d_changed, dl, d.num_cus, s)) != hipSuccess)
-        return e2;
     }
-    return hipSuccess;
+    b.dist = d.wdist.p;
+    b.nh = d.wnh.p;
+    b.nh_bytes = nb;
+    b.nh_bits = ctx->nh_bits;
+    b.ovf_list = d.ovf.p;
+    b.work = d.work.p;
+    // the rounds kernel starts each unit from its source's base rows (only the nodes the
+    // failed links push back are re-solved); other kernels solve from scratch
+    b.seed_dist = d.base_dist.p;
+    b.seed_tight = d.base_tight.p;
+    b.seed_unit = d.wunit.p + off;
+    b.seed_nsrc = n_src;
+    b.seed_tin = base_tin ? d.base_tin.p : nullptr;
+    // ... and compares each solve with the base rows itself (no rows through HBM)
+    const bool fused = ign_plan.rounds && !ign_plan.exact && !ign_plan.bfs;
+    if (fused) {
+      b.seed_nh = d.base_nh.p;
+      b.seed_changed = d_changed;
+      b.delta = dl;
+    }
+    // OPENR_SPF_PROF (tuning aid, link-set sweeps): the seeded re-solves' phase records
+    const bool prof = fused && set_links && prof_enabled();
+    if (prof) {
+      const size_t bytes = 10 * (size_t)m * sizeof(unsigned long long);
+      if ((e2 = hipMallocAsync(reinterpret_cast<void**>(&b.prof_solve), bytes, s)) != hipSuccess) return e2;
+      if ((e2 = hipMemsetAsync(b.prof_solve, 0, bytes, s)) != hipSuccess) return e2;
+    }
+    if ((e2 = launch(ctx, d, ign_plan, b, s)) != hipSuccess) return e2;
+    if (prof) {
+      const size_t at = prof_rec.size();
+      prof_rec.resize(at + 10 * (size_t)m);
+      if ((e2 = hipMemcpyAsync(prof_rec.data() + at, b.prof_solve, 10 * (size_t)m * sizeof(unsigned long long),
+                               hipMemcpyDeviceToHost, s)) != hipSuccess)
+        return e2;
+      if ((e2 = hipStreamSynchronize(s)) != hipSuccess) return e2;
+      if ((e2 = hipFreeAsync(b.prof_solve, s)) != hipSuccess) return e2;
+    }
+    if (!fused && (e2 = launch_rows_compare(m, V, nb, d.wdist.p, d.wnh.p, d.base_dist.p, d.base_nh.p, d.wunit.p + off, n_src,
+                                  d_changed, dl, d.num_cus, s)) != hipSuccess)
+      return e2;
+  }
+  if (!prof_rec.empty()) print_resolve_prof(prof_rec, (uint32_t)(prof_rec.size() / 10));
+  return hipSuccess;
+}
+
+// Per-link-failure what-if sweep on one device (spf_sweep.hip has the unit semantics):
+// base SPF with tight edges -> filter of the affected units -> chunks of single-link
+// ignore-set solves through the ordinary launcher -> row comparison against the base.
+// Reads the affected-unit count back (one stream sync) to size the chunks.
+hipError_t whatif_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, const Plan& ign_plan,
+                            const uint32_t* d_links, uint32_t n_links, const uint32_t* d_sources, uint32_t n_src,
+                            uint32_t* d_changed, hipStream_t s, uint32_t* solved, bool use_link_metric,
+                            const WhatifDelta& dl = WhatifDelta{}) {
+  const uint32_t V = ctx->V;
+  const uint32_t nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
+  *solved = 0;
+  if (!n_src || !n_links) return hipSuccess;
+  hipError_t err;
+  bool base_tin = false;
+  OPENR_TRY(whatif_base_solve(ctx, d, base_plan, d_sources, n_src, s, &base_tin));
+  auto resolve_units = [&](uint32_t count, uint32_t base) -> hipError_t {
+    return whatif_resolve_units(ctx, d, ign_plan, count, base, nullptr, n_src, base_tin, d_changed, dl, s);
   };
   const char* mode = std::getenv("OPENR_SPF_WHATIF");
   const bool dist64 = use_link_metric && (uint64_t)V * ctx->w_max >= 0xFFFFFFFFull;
@@ -675,52 +773,7 @@ hipError_t whatif_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan
           std::vector<unsigned long long> h(10 * (size_t)nres);
           OPENR_TRY(hipMemcpy(h.data(), b.prof_solve, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
           OPENR_TRY(hipFreeAsync(b.prof_solve, s));
-          if (nres) {
-            unsigned long long t0 = ~0ull, t1 = 0;
-            double ph[7] = {0}, na = 0, rd = 0, rk = 0, tot = 0;
-            for (uint32_t k = 0; k < nres; ++k) {
-              const unsigned long long* x = &h[10 * (size_t)k];
-              t0 = std::min(t0, x[0]);
-              t1 = std::max(t1, x[7]);
-              for (int q = 0; q < 7; ++q) ph[q] += (double)(x[q + 1] - x[q]) / 100.0;
-              tot += (double)(x[7] - x[0]) / 100.0;
-              na += (double)x[8];
-              rd += (double)(x[9] & 0xFFFFFFFFull);
-              rk += (double)(x[9] >> 32);
-            }
-            std::fprintf(stderr,
-                         "[whatif resolve] n=%u span=%.1fus mean solve %.1fus: seed-a %.1f seed-A %.1f seed-c %.1f "
-                         "dist %.1f indeg %.1f kahn %.1f compare %.1f | |A| %.1f, rounds: A+c+dist %.1f, kahn %.1f, "
-                         "concurrency %.0f\n",
-                         nres, (t1 - t0) / 100.0, tot / nres, ph[0] / nres, ph[1] / nres, ph[2] / nres, ph[3] / nres,
-                         ph[4] / nres, ph[5] / nres, ph[6] / nres, na / nres, rd / nres, rk / nres,
-                         tot / ((t1 - t0) / 100.0));
-            // duration spread, its correlation with |A|, and the solves running over the span
-            std::vector<double> dur(nres), asz(nres);
-            for (uint32_t k = 0; k < nres; ++k) {
-              dur[k] = (double)(h[10 * (size_t)k + 7] - h[10 * (size_t)k]) / 100.0;
-              asz[k] = (double)h[10 * (size_t)k + 8];
-            }
-            std::vector<double> srt = dur;
-            std::sort(srt.begin(), srt.end());
-            const double md = tot / nres, ma = na / nres;
-            double sxy = 0, sxx = 0, syy = 0;
-            for (uint32_t k = 0; k < nres; ++k) {
-              sxy += (dur[k] - md) * (asz[k] - ma);
-              sxx += (dur[k] - md) * (dur[k] - md);
-              syy += (asz[k] - ma) * (asz[k] - ma);
-            }
-            std::fprintf(stderr, "  duration p10 %.1f p50 %.1f p90 %.1f max %.1f us; corr(duration, |A|) %.2f; running at",
-                         srt[nres / 10], srt[nres / 2], srt[nres * 9 / 10], srt.back(),
-                         sxx > 0 && syy > 0 ? sxy / std::sqrt(sxx * syy) : 0.0);
-            for (int q : {10, 25, 50, 75, 90, 95}) {
-              const unsigned long long tq = t0 + (t1 - t0) * q / 100;
-              uint32_t live = 0;
-              for (uint32_t k = 0; k < nres; ++k) live += (h[10 * (size_t)k] <= tq && h[10 * (size_t)k + 7] > tq) ? 1u : 0u;
-              std::fprintf(stderr, " %d%%:%u", q, live);
-            }
-            std::fprintf(stderr, "\n");
-          }
+          print_resolve_prof(h, nres);
         }
       }
       uint32_t cnt[2] = {0, 0};  // affected units, units past the slots
@@ -754,9 +807,48 @@ hipError_t whatif_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan
                               !use_link_metric, dist64, d_changed, d.work.p + kIncrCtr, d.num_cus, s);
   }
   return resolve_units(count, 0);
-#undef OPENR_TRY
-  return hipSuccess;
 }
+
+// Link-set what-if sweep on one device (openr_spf_whatif_sets; whatif_set_filter in
+// spf_sweep.hip has the unit semantics): unit (i, j) fails every link of set i =
+// d_set_links[d_set_ptr[i], d_set_ptr[i + 1]) for d_sources[j]. Base SPF with tight edges ->
+// set filter (source-major work list that points each affected unit at its set) -> the
+// count read back (one stream sync) -> chunked re-solves with the unit's set as ignore set:
+// on the rounds plan seeded from the base rows with the compare and the delta fused, on
+// every other plan (BFS families, fringe, exact order) plain solves + rows_compare.
+// Neither the grouped nor the incremental repair is set-aware: every affected unit is
+// re-solved.
+hipError_t whatif_sets_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, const Plan& ign_plan,
+                                 const uint32_t* d_set_ptr, const uint32_t* d_set_links, uint32_t n_sets,
+                                 uint32_t n_set_links, const uint32_t* d_sources, uint32_t n_src, uint32_t* d_changed,
+                                 hipStream_t s,
+                                 uint32_t* solved, bool use_link_metric, const WhatifDelta& dl = WhatifDelta{}) {
+  *solved = 0;
+  if (!n_src || !n_sets) return hipSuccess;
+  const size_t units = (size_t)n_sets * n_src;
+  if (units > 0xFFFFFFFFull) return hipErrorInvalidValue;  // unit ids are u32
+  hipError_t err;
+  bool base_tin = false;
+  OPENR_TRY(whatif_base_solve(ctx, d, base_plan, d_sources, n_src, s, &base_tin));
+  OPENR_TRY(d.wsrc.reserve(units));
+  OPENR_TRY(d.wunit.reserve(units));
+  OPENR_TRY(d.wbeg.reserve(units));
+  OPENR_TRY(d.wend.reserve(units));
+  OPENR_TRY(d.wcount.reserve(1));
+  // zero or wrapped metrics on an exact-order plan: the pop order depends on every
+  // relaxation, so every unit whose set holds a link of the graph is re-solved
+  const bool exact = base_plan.exact || ign_plan.exact;
+  const uint64_t* filter_tight = (exact && !ctx->metric_ok && use_link_metric) ? nullptr : d.base_tight.p;
+  OPENR_TRY(launch_whatif_set_filter(d.g, d_set_ptr, d_set_links, n_sets, n_set_links, d_sources, n_src, filter_tight, d_changed,
+                                     d.wsrc.p, d.wunit.p, d.wbeg.p, d.wend.p, d.wcount.p, d.num_cus, s));
+  uint32_t count = 0;
+  OPENR_TRY(hipMemcpyAsync(&count, d.wcount.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  OPENR_TRY(hipStreamSynchronize(s));
+  *solved = count;
+  if (!count) return hipSuccess;
+  return whatif_resolve_units(ctx, d, ign_plan, count, 0, d_set_links, n_src, base_tin, d_changed, dl, s);
+}
+#undef OPENR_TRY
 
 // Bytes of second-SPF distance rows a KSP2 batch may hold on a device at once.
 constexpr size_t kKspChunkBytes = size_t(8) << 30;  // second-SPF rows + ignore slots per chunk
@@ -992,12 +1084,30 @@ int whatif_plans(openr_spf_ctx* ctx, uint32_t flags, Plan* base_plan, Plan* ign_
   return make_plan(ctx, flags, true, ign_plan);
 }
 
-// openr_spf_whatif_delta[_device] on one device: the sweep with the delta into library
+// The failure units of a what-if sweep on one device: n single links (links), or n link
+// sets in CSR form (set_ptr != nullptr: set i = set_links[set_ptr[i], set_ptr[i + 1])).
+struct WhatifUnits {
+  const uint32_t* links = nullptr;
+  const uint32_t* set_ptr = nullptr;
+  const uint32_t* set_links = nullptr;
+  uint32_t n_set_links = 0;  // entries of set_links (the filter clamps every slice to them)
+  uint32_t n = 0;
+};
+
+hipError_t whatif_units_on_device(openr_spf_ctx* ctx, Device& d, const Plan& bp, const Plan& ip, const WhatifUnits& un,
+                                  const uint32_t* d_sources, uint32_t n_src, uint32_t* d_changed, hipStream_t s,
+                                  uint32_t* solved, bool use_link_metric, const WhatifDelta& dl = WhatifDelta{}) {
+  if (un.set_ptr)
+    return whatif_sets_on_device(ctx, d, bp, ip, un.set_ptr, un.set_links, un.n, un.n_set_links, d_sources, n_src, d_changed, s,
+                                 solved, use_link_metric, dl);
+  return whatif_on_device(ctx, d, bp, ip, un.links, un.n, d_sources, n_src, d_changed, s, solved, use_link_metric, dl);
+}
+
+// openr_spf_whatif[_sets]_delta[_device] on one device: the sweep with the delta into library
 // scratch (per-unit slots, WhatifDelta), the exclusive scan of changed into d_ptr, then
 // (when the total fits `cap`) every unit's entries gathered into the caller's CSR arrays.
 // Synchronizes s. *total = sum(changed); OPENR_SPF_E2BIG when it exceeds cap.
-int whatif_delta_on_device(openr_spf_ctx* ctx, Device& d, const uint32_t* d_links, uint32_t n_links,
-                           const uint32_t* d_sources, uint32_t n_src, uint32_t flags, uint32_t* d_changed,
+int whatif_delta_on_device(openr_spf_ctx* ctx, Device& d, const WhatifUnits& un, const uint32_t* d_sources, uint32_t n_src, uint32_t flags, uint32_t* d_changed,
                            uint64_t* d_ptr, uint32_t* d_node, unsigned long long* d_dist, uint8_t* d_nh, uint64_t cap,
                            uint32_t nhb, hipStream_t s, uint64_t* total, uint64_t* solved_out) {
   const uint32_t nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
@@ -1005,7 +1115,7 @@ int whatif_delta_on_device(openr_spf_ctx* ctx, Device& d, const uint32_t* d_link
   Plan bp, ip;
   int rc = whatif_plans(ctx, flags, &bp, &ip);
   if (rc) return rc;
-  const size_t units = (size_t)n_links * n_src;
+  const size_t units = (size_t)un.n * n_src;
   *total = 0;
   *solved_out = 0;
   unsigned long long* ptr = reinterpret_cast<unsigned long long*>(d_ptr);
@@ -1033,8 +1143,8 @@ int whatif_delta_on_device(openr_spf_ctx* ctx, Device& d, const uint32_t* d_link
   dl.nhb = nhb;
   dl.used = d.dl_used.p;
   uint32_t solved = 0;
-  HIP_TRY(whatif_on_device(ctx, d, bp, ip, d_links, n_links, d_sources, n_src, d_changed, s, &solved,
-                           (flags & OPENR_SPF_USE_LINK_METRIC) != 0, dl));
+  HIP_TRY(whatif_units_on_device(ctx, d, bp, ip, un, d_sources, n_src, d_changed, s, &solved,
+                                 (flags & OPENR_SPF_USE_LINK_METRIC) != 0, dl));
   HIP_TRY(launch_delta_scan(d_changed, units, d.dl_tsum.p, ptr, s));
   unsigned long long tu[2] = {0, 0};  // total entries, pool slots used
   HIP_TRY(hipMemcpyAsync(&tu[0], ptr + units, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
@@ -1053,6 +1163,259 @@ int whatif_delta_on_device(openr_spf_ctx* ctx, Device& d, const uint32_t* d_link
   return OPENR_SPF_OK;
 }
 
+// Argument checks of the host what-if forms (hu in host memory: single links or link sets).
+int check_whatif_host(const openr_spf_ctx* ctx, const WhatifUnits& hu, const uint32_t* sources, uint32_t n_sources,
+                      const uint32_t* changed) {
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if ((hu.n && !hu.links && !hu.set_ptr) || (n_sources && !sources) || (hu.n && n_sources && !changed))
+    return fail(OPENR_SPF_EINVAL, "null links, sources or changed");
+  for (uint32_t i = 0; i < n_sources; ++i)
+    if (sources[i] >= ctx->V) return fail(OPENR_SPF_EINVAL, "source %u out of range (V=%u)", sources[i], ctx->V);
+  if (!hu.set_ptr) {
+    for (uint32_t i = 0; i < hu.n; ++i)
+      if (hu.links[i] >= ctx->L)
+        return fail(OPENR_SPF_EINVAL, "link %u out of range (L=%u)", hu.links[i], ctx->L);
+    return OPENR_SPF_OK;
+  }
+  for (uint32_t i = 0; i < hu.n; ++i)
+    if (hu.set_ptr[i + 1] < hu.set_ptr[i]) return fail(OPENR_SPF_EINVAL, "set_ptr does not ascend at set %u", i);
+  if (hu.set_ptr[hu.n] > hu.set_ptr[0] && !hu.set_links) return fail(OPENR_SPF_EINVAL, "null set_links");
+  for (uint32_t k = hu.set_ptr[0]; k < hu.set_ptr[hu.n]; ++k)
+    if (hu.set_links[k] >= ctx->L)
+      return fail(OPENR_SPF_EINVAL, "link %u out of range (L=%u)", hu.set_links[k], ctx->L);
+  return OPENR_SPF_OK;
+}
+
+// Units [b, b + m) of hu into the device's input buffers on its stream (*un: the device
+// view). A block of sets takes its slice of set_links, and its set_ptr rebased to that slice.
+int upload_whatif_units(Device& d, const WhatifUnits& hu, uint32_t b, uint32_t m, std::vector<uint32_t>* rebased,
+                        WhatifUnits* un) {
+  *un = WhatifUnits{};
+  un->n = m;
+  if (!hu.set_ptr) {
+    HIP_TRY(d.win_links.reserve(m));
+    HIP_TRY(hipMemcpyAsync(d.win_links.p, hu.links + b, m * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    un->links = d.win_links.p;
+    return OPENR_SPF_OK;
+  }
+  const uint32_t lb = hu.set_ptr[b], le = hu.set_ptr[b + m];
+  rebased->resize(m + 1);
+  for (uint32_t i = 0; i <= m; ++i) (*rebased)[i] = hu.set_ptr[b + i] - lb;
+  HIP_TRY(d.win_ptr.reserve(m + 1));
+  HIP_TRY(d.win_links.reserve(std::max<uint32_t>(le - lb, 1u)));
+  HIP_TRY(hipMemcpyAsync(d.win_ptr.p, rebased->data(), (m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+  if (le > lb)
+    HIP_TRY(hipMemcpyAsync(d.win_links.p, hu.set_links + lb, (le - lb) * sizeof(uint32_t), hipMemcpyHostToDevice,
+                           d.stream));
+  HIP_TRY(hipStreamSynchronize(d.stream));  // `rebased` is reused for the next device's block
+  un->set_ptr = d.win_ptr.p;
+  un->set_links = d.win_links.p;
+  un->n_set_links = le - lb;
+  return OPENR_SPF_OK;
+}
+
+// openr_spf_whatif / openr_spf_whatif_sets: units split in contiguous blocks across the devices
+int whatif_host(openr_spf_ctx* ctx, const WhatifUnits& hu, const uint32_t* sources, uint32_t n_sources,
+                uint32_t flags, uint32_t* changed, uint64_t* out_solved) {
+  const uint32_t n_links = hu.n;
+  int rc = check_whatif_host(ctx, hu, sources, n_sources, changed);
+  if (rc) return rc;
+  Plan bp, ip;
+  rc = whatif_plans(ctx, flags, &bp, &ip);
+  if (rc) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  // links (or sets) are split in contiguous blocks across the context's devices
+  std::vector<uint32_t> rebased;
+  const uint32_t nd = (uint32_t)ctx->devs.size();
+  const uint32_t per = (n_links + nd - 1) / std::max<uint32_t>(nd, 1);
+  uint64_t solved_total = 0;
+  for (uint32_t di = 0; di < nd; ++di) {
+    Device& d = ctx->devs[di];
+    const uint32_t b = std::min(n_links, di * per), e = std::min(n_links, b + per), m = e - b;
+    if (!m || !n_sources) continue;
+    HIP_TRY(hipSetDevice(d.ordinal));
+    WhatifUnits un;
+    if ((rc = upload_whatif_units(d, hu, b, m, &rebased, &un)) != OPENR_SPF_OK) return rc;
+    HIP_TRY(d.win_src.reserve(n_sources));
+    HIP_TRY(d.wchanged.reserve((size_t)m * n_sources));
+    HIP_TRY(hipMemcpyAsync(d.win_src.p, sources, n_sources * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    uint32_t solved = 0;
+    HIP_TRY(whatif_units_on_device(ctx, d, bp, ip, un, d.win_src.p, n_sources, d.wchanged.p, d.stream, &solved,
+                                   (flags & OPENR_SPF_USE_LINK_METRIC) != 0));
+    HIP_TRY(hipMemcpyAsync(changed + (size_t)b * n_sources, d.wchanged.p, (size_t)m * n_sources * sizeof(uint32_t),
+                           hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    solved_total += solved + n_sources;
+  }
+  ctx->stats.spf_runs += solved_total;
+  ctx->stats.batches += 1;
+  ctx->stats.last_batch_ms =
+      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (out_solved) *out_solved = solved_total;
+  return OPENR_SPF_OK;
+}
+
+// openr_spf_whatif_delta / openr_spf_whatif_sets_delta
+int whatif_delta_host(openr_spf_ctx* ctx, const WhatifUnits& hu, const uint32_t* sources, uint32_t n_sources,
+                      uint32_t flags, uint32_t* changed, openr_spf_whatif_delta_t* delta, uint64_t* out_solved) {
+  const uint32_t n_links = hu.n;
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (!delta || !delta->ptr) return fail(OPENR_SPF_EINVAL, "null delta or delta->ptr");
+  int rc0 = check_whatif_host(ctx, hu, sources, n_sources, changed);
+  if (rc0) return rc0;
+  if (delta->cap && (!delta->node || !delta->dist || !delta->nh))
+    return fail(OPENR_SPF_EINVAL, "null delta->node, dist or nh");
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint32_t nhb = delta->nh_bytes;
+  // links (or sets) split in contiguous blocks across the devices (openr_spf_whatif); each
+  // device's CSR is appended to the caller's at the running total
+  std::vector<uint32_t> rebased;
+  const uint32_t nd = (uint32_t)ctx->devs.size();
+  const uint32_t per = (n_links + nd - 1) / std::max<uint32_t>(nd, 1);
+  uint64_t solved_total = 0, at = 0;
+  bool over = false;
+  delta->ptr[0] = 0;
+  std::vector<uint64_t> ptr;
+  std::vector<uint32_t> idx;
+  for (uint32_t di = 0; di < nd; ++di) {
+    Device& d = ctx->devs[di];
+    const uint32_t b = std::min(n_links, di * per), e = std::min(n_links, b + per), m = e - b;
+    if (!m || !n_sources) continue;
+    const size_t mu = (size_t)m * n_sources;
+    HIP_TRY(hipSetDevice(d.ordinal));
+    WhatifUnits un;
+    if ((rc0 = upload_whatif_units(d, hu, b, m, &rebased, &un)) != OPENR_SPF_OK) return rc0;
+    HIP_TRY(d.win_src.reserve(n_sources));
+    HIP_TRY(d.wchanged.reserve(mu));
+    HIP_TRY(d.dlo_ptr.reserve(mu + 1));
+    HIP_TRY(hipMemcpyAsync(d.win_src.p, sources, n_sources * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    // the device's entries land in library buffers sized to the room left in the caller's
+    const uint64_t room = delta->cap > at ? delta->cap - at : 0;
+    HIP_TRY(d.dlo_node.reserve(std::max<uint64_t>(room, 1)));
+    HIP_TRY(d.dlo_dist.reserve(std::max<uint64_t>(room, 1)));
+    HIP_TRY(d.dlo_nh.reserve(std::max<uint64_t>(room * nhb, 1)));
+    uint64_t total = 0, solved = 0;
+    int rc = whatif_delta_on_device(ctx, d, un, d.win_src.p, n_sources, flags, d.wchanged.p,
+                                    reinterpret_cast<uint64_t*>(d.dlo_ptr.p), d.dlo_node.p, d.dlo_dist.p, d.dlo_nh.p,
+                                    room, nhb, d.stream, &total, &solved);
+    if (rc && rc != OPENR_SPF_E2BIG) return rc;
+    over |= rc == OPENR_SPF_E2BIG;
+    solved_total += solved;
+    ptr.resize(mu + 1);
+    HIP_TRY(hipMemcpyAsync(changed + (size_t)b * n_sources, d.wchanged.p, mu * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                           d.stream));
+    HIP_TRY(hipMemcpyAsync(ptr.data(), d.dlo_ptr.p, (mu + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+    const bool fits = !over && total <= room;
+    if (fits && total) {
+      HIP_TRY(hipMemcpyAsync(delta->node + at, d.dlo_node.p, total * 4u, hipMemcpyDeviceToHost, d.stream));
+      HIP_TRY(hipMemcpyAsync(delta->dist + at, d.dlo_dist.p, total * 8u, hipMemcpyDeviceToHost, d.stream));
+      HIP_TRY(hipMemcpyAsync(delta->nh + at * nhb, d.dlo_nh.p, total * nhb, hipMemcpyDeviceToHost, d.stream));
+    }
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    for (size_t u = 0; u < mu; ++u) {
+      const size_t gu = (size_t)b * n_sources + u;
+      delta->ptr[gu + 1] = at + ptr[u + 1];
+      const uint32_t c = (uint32_t)(ptr[u + 1] - ptr[u]);
+      if (!fits || c < 2) continue;
+      // each unit's nodes ascending (the device keeps the repair's order)
+      const uint64_t o = at + ptr[u];
+      bool sorted = true;
+      for (uint32_t k = 1; k < c && sorted; ++k) sorted = delta->node[o + k - 1] < delta->node[o + k];
+      if (sorted) continue;
+      idx.resize(c);
+      for (uint32_t k = 0; k < c; ++k) idx[k] = k;
+      std::sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return delta->node[o + x] < delta->node[o + y]; });
+      std::vector<uint32_t> tn(c);
+      std::vector<uint64_t> td(c);
+      std::vector<uint8_t> th((size_t)c * nhb);
+      for (uint32_t k = 0; k < c; ++k) {
+        tn[k] = delta->node[o + idx[k]];
+        td[k] = delta->dist[o + idx[k]];
+        std::memcpy(&th[(size_t)k * nhb], delta->nh + (o + idx[k]) * nhb, nhb);
+      }
+      std::memcpy(delta->node + o, tn.data(), c * 4u);
+      std::memcpy(delta->dist + o, td.data(), c * 8u);
+      std::memcpy(delta->nh + o * nhb, th.data(), (size_t)c * nhb);
+    }
+    at += total;
+  }
+  ctx->stats.last_batch_ms =
+      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (out_solved) *out_solved = solved_total;
+  if (over || at > delta->cap)
+    return fail(OPENR_SPF_E2BIG, "delta needs %llu entries, cap %llu (ptr and changed are filled, entries are not)",
+                (unsigned long long)at, (unsigned long long)delta->cap);
+  return OPENR_SPF_OK;
+}
+
+
+// openr_spf_whatif_device / openr_spf_whatif_sets_device (un in device memory)
+int whatif_device_form(openr_spf_ctx* ctx, int device_index, const WhatifUnits& un, const uint32_t* d_sources,
+                       uint32_t n_sources, uint32_t flags, uint32_t* d_changed, void* stream, uint64_t* out_solved) {
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (device_index < 0 || device_index >= (int)ctx->devs.size())
+    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+  if ((un.n && !un.links && !un.set_ptr) || (n_sources && !d_sources) || (un.n && n_sources && !d_changed))
+    return fail(OPENR_SPF_EINVAL, "null links, sources or changed");
+  Plan bp, ip;
+  int rc = whatif_plans(ctx, flags, &bp, &ip);
+  if (rc) return rc;
+  Device& d = ctx->devs[device_index];
+  HIP_TRY(hipSetDevice(d.ordinal));
+  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d.stream;
+  uint32_t solved = 0;
+  HIP_TRY(whatif_units_on_device(ctx, d, bp, ip, un, d_sources, n_sources, d_changed, s, &solved,
+                                 (flags & OPENR_SPF_USE_LINK_METRIC) != 0));
+  const uint64_t total = un.n && n_sources ? (uint64_t)solved + n_sources : 0u;
+  ctx->stats.spf_runs += total;
+  ctx->stats.batches += 1;
+  if (out_solved) *out_solved = total;
+  return OPENR_SPF_OK;
+}
+
+// openr_spf_whatif_delta_device / openr_spf_whatif_sets_delta_device
+int whatif_delta_device_form(openr_spf_ctx* ctx, int device_index, const WhatifUnits& un, const uint32_t* d_sources,
+                             uint32_t n_sources, uint32_t flags, uint32_t* d_changed, uint64_t* d_ptr,
+                             uint32_t* d_node, uint64_t* d_dist, uint8_t* d_nh, uint64_t cap, uint32_t nh_bytes,
+                             void* stream, uint64_t* out_total, uint64_t* out_solved) {
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (device_index < 0 || device_index >= (int)ctx->devs.size())
+    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+  if ((un.n && !un.links && !un.set_ptr) || (n_sources && !d_sources) || (un.n && n_sources && !d_changed) || !d_ptr)
+    return fail(OPENR_SPF_EINVAL, "null links, sources, changed or ptr");
+  if (cap && (!d_node || !d_dist || !d_nh)) return fail(OPENR_SPF_EINVAL, "null delta buffer");
+  Device& d = ctx->devs[device_index];
+  HIP_TRY(hipSetDevice(d.ordinal));
+  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d.stream;
+  uint64_t total = 0, solved = 0;
+  const int rc = whatif_delta_on_device(ctx, d, un, d_sources, n_sources, flags, d_changed, d_ptr, d_node,
+                                        reinterpret_cast<unsigned long long*>(d_dist), d_nh, cap, nh_bytes, s, &total,
+                                        &solved);
+  if (out_total) *out_total = total;
+  if (out_solved) *out_solved = solved;
+  return rc;
+}
+
+WhatifUnits host_sets(const uint32_t* set_ptr, const uint32_t* set_links, uint32_t n_sets) {
+  WhatifUnits hu;
+  hu.set_ptr = n_sets ? set_ptr : nullptr;
+  hu.set_links = set_links;
+  hu.n = n_sets;
+  return hu;
+}
+
+WhatifUnits device_sets(const uint32_t* d_set_ptr, const uint32_t* d_set_links, uint32_t n_sets, uint32_t n_set_links) {
+  WhatifUnits un;
+  un.set_ptr = n_sets ? d_set_ptr : nullptr;
+  un.set_links = d_set_links;
+  un.n_set_links = n_set_links;
+  un.n = n_sets;
+  return un;
+}
 
 }  // namespace
 
@@ -1163,6 +1526,9 @@ void openr_spf_destroy(openr_spf_ctx* ctx) {
     d.dlo_dist.release();
     d.dlo_node.release();
     d.dlo_nh.release();
+    d.wbeg.release();
+    d.wend.release();
+    d.win_ptr.release();
     void* sweep[] = {d.base_dist.p, d.base_tight.p, d.wdist.p, d.base_nh.p, d.wnh.p, d.wsrc.p, d.wlink.p,
                      d.wunit.p,     d.wcount.p,     d.wiota.p, d.base_tin.p, d.win_links.p, d.win_src.p, d.wchanged.p, d.wchanged_t.p,
                      d.kbase.p,     d.krows.p,      d.krows16.p, d.kign.p,  d.kend.p, d.ksrc.p,      d.kptr.p,    d.kstatus.p,
@@ -1863,190 +2229,79 @@ int openr_spf_take_status(openr_spf_ctx* ctx, int device_index, uint32_t* out_st
 
 int openr_spf_whatif(openr_spf_ctx* ctx, const uint32_t* links, uint32_t n_links, const uint32_t* sources,
                      uint32_t n_sources, uint32_t flags, uint32_t* changed, uint64_t* out_solved) {
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if ((n_links && !links) || (n_sources && !sources) || (n_links && n_sources && !changed))
-    return fail(OPENR_SPF_EINVAL, "null links, sources or changed");
-  for (uint32_t i = 0; i < n_sources; ++i)
-    if (sources[i] >= ctx->V) return fail(OPENR_SPF_EINVAL, "source %u out of range (V=%u)", sources[i], ctx->V);
-  for (uint32_t i = 0; i < n_links; ++i)
-    if (links[i] >= ctx->L) return fail(OPENR_SPF_EINVAL, "link %u out of range (L=%u)", links[i], ctx->L);
-  Plan bp, ip;
-  int rc = whatif_plans(ctx, flags, &bp, &ip);
-  if (rc) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
-  // links are split in contiguous blocks across the context's devices
-  const uint32_t nd = (uint32_t)ctx->devs.size();
-  const uint32_t per = (n_links + nd - 1) / std::max<uint32_t>(nd, 1);
-  uint64_t solved_total = 0;
-  for (uint32_t di = 0; di < nd; ++di) {
-    Device& d = ctx->devs[di];
-    const uint32_t b = std::min(n_links, di * per), e = std::min(n_links, b + per), m = e - b;
-    if (!m || !n_sources) continue;
-    HIP_TRY(hipSetDevice(d.ordinal));
-    HIP_TRY(d.win_links.reserve(m));
-    HIP_TRY(d.win_src.reserve(n_sources));
-    HIP_TRY(d.wchanged.reserve((size_t)m * n_sources));
-    HIP_TRY(hipMemcpyAsync(d.win_links.p, links + b, m * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
-    HIP_TRY(hipMemcpyAsync(d.win_src.p, sources, n_sources * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
-    uint32_t solved = 0;
-    HIP_TRY(whatif_on_device(ctx, d, bp, ip, d.win_links.p, m, d.win_src.p, n_sources, d.wchanged.p, d.stream,
-                             &solved, (flags & OPENR_SPF_USE_LINK_METRIC) != 0));
-    HIP_TRY(hipMemcpyAsync(changed + (size_t)b * n_sources, d.wchanged.p, (size_t)m * n_sources * sizeof(uint32_t),
-                           hipMemcpyDeviceToHost, d.stream));
-    HIP_TRY(hipStreamSynchronize(d.stream));
-    solved_total += solved + n_sources;
-  }
-  ctx->stats.spf_runs += solved_total;
-  ctx->stats.batches += 1;
-  ctx->stats.last_batch_ms =
-      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (out_solved) *out_solved = solved_total;
-  return OPENR_SPF_OK;
+  WhatifUnits hu;
+  hu.links = links;
+  hu.n = n_links;
+  return whatif_host(ctx, hu, sources, n_sources, flags, changed, out_solved);
+}
+
+int openr_spf_whatif_sets(openr_spf_ctx* ctx, const uint32_t* set_ptr, const uint32_t* set_links, uint32_t n_sets,
+                          const uint32_t* sources, uint32_t n_sources, uint32_t flags, uint32_t* changed,
+                          uint64_t* out_solved) {
+  clear_launch_trace();
+  if (n_sets && !set_ptr) return fail(OPENR_SPF_EINVAL, "null set_ptr");
+  return whatif_host(ctx, host_sets(set_ptr, set_links, n_sets), sources, n_sources, flags, changed, out_solved);
 }
 
 int openr_spf_whatif_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_links, uint32_t n_links,
                             const uint32_t* d_sources, uint32_t n_sources, uint32_t flags, uint32_t* d_changed,
                             void* stream, uint64_t* out_solved) {
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (device_index < 0 || device_index >= (int)ctx->devs.size())
-    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
-  if ((n_links && !d_links) || (n_sources && !d_sources) || (n_links && n_sources && !d_changed))
-    return fail(OPENR_SPF_EINVAL, "null links, sources or changed");
-  Plan bp, ip;
-  int rc = whatif_plans(ctx, flags, &bp, &ip);
-  if (rc) return rc;
-  Device& d = ctx->devs[device_index];
-  HIP_TRY(hipSetDevice(d.ordinal));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d.stream;
-  uint32_t solved = 0;
-  HIP_TRY(whatif_on_device(ctx, d, bp, ip, d_links, n_links, d_sources, n_sources, d_changed, s, &solved,
-                           (flags & OPENR_SPF_USE_LINK_METRIC) != 0));
-  const uint64_t total = n_links && n_sources ? (uint64_t)solved + n_sources : 0u;
-  ctx->stats.spf_runs += total;
-  ctx->stats.batches += 1;
-  if (out_solved) *out_solved = total;
-  return OPENR_SPF_OK;
+  WhatifUnits un;
+  un.links = d_links;
+  un.n = n_links;
+  return whatif_device_form(ctx, device_index, un, d_sources, n_sources, flags, d_changed, stream, out_solved);
+}
+
+int openr_spf_whatif_sets_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_set_ptr,
+                                 const uint32_t* d_set_links, uint32_t n_sets, uint32_t n_set_links,
+                                 const uint32_t* d_sources, uint32_t n_sources, uint32_t flags, uint32_t* d_changed,
+                                 void* stream, uint64_t* out_solved) {
+  clear_launch_trace();
+  if (n_sets && (!d_set_ptr || (n_set_links && !d_set_links))) return fail(OPENR_SPF_EINVAL, "null set_ptr or set_links");
+  return whatif_device_form(ctx, device_index, device_sets(d_set_ptr, d_set_links, n_sets, n_set_links), d_sources,
+                            n_sources, flags, d_changed, stream, out_solved);
 }
 
 int openr_spf_whatif_delta_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_links, uint32_t n_links,
                                   const uint32_t* d_sources, uint32_t n_sources, uint32_t flags, uint32_t* d_changed,
                                   uint64_t* d_ptr, uint32_t* d_node, uint64_t* d_dist, uint8_t* d_nh, uint64_t cap,
                                   uint32_t nh_bytes, void* stream, uint64_t* out_total, uint64_t* out_solved) {
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (device_index < 0 || device_index >= (int)ctx->devs.size())
-    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
-  if ((n_links && !d_links) || (n_sources && !d_sources) || (n_links && n_sources && !d_changed) || !d_ptr)
-    return fail(OPENR_SPF_EINVAL, "null links, sources, changed or ptr");
-  if (cap && (!d_node || !d_dist || !d_nh)) return fail(OPENR_SPF_EINVAL, "null delta buffer");
-  Device& d = ctx->devs[device_index];
-  HIP_TRY(hipSetDevice(d.ordinal));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d.stream;
-  uint64_t total = 0, solved = 0;
-  const int rc = whatif_delta_on_device(ctx, d, d_links, n_links, d_sources, n_sources, flags, d_changed, d_ptr,
-                                        d_node, reinterpret_cast<unsigned long long*>(d_dist), d_nh, cap, nh_bytes,
-                                        s, &total, &solved);
-  if (out_total) *out_total = total;
-  if (out_solved) *out_solved = solved;
-  return rc;
+  WhatifUnits un;
+  un.links = d_links;
+  un.n = n_links;
+  return whatif_delta_device_form(ctx, device_index, un, d_sources, n_sources, flags, d_changed, d_ptr, d_node, d_dist,
+                                  d_nh, cap, nh_bytes, stream, out_total, out_solved);
+}
+
+int openr_spf_whatif_sets_delta_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_set_ptr,
+                                       const uint32_t* d_set_links, uint32_t n_sets, uint32_t n_set_links,
+                                       const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                                       uint32_t* d_changed, uint64_t* d_ptr, uint32_t* d_node, uint64_t* d_dist,
+                                       uint8_t* d_nh, uint64_t cap, uint32_t nh_bytes, void* stream,
+                                       uint64_t* out_total, uint64_t* out_solved) {
+  clear_launch_trace();
+  if (n_sets && (!d_set_ptr || (n_set_links && !d_set_links))) return fail(OPENR_SPF_EINVAL, "null set_ptr or set_links");
+  return whatif_delta_device_form(ctx, device_index, device_sets(d_set_ptr, d_set_links, n_sets, n_set_links),
+                                  d_sources, n_sources, flags, d_changed, d_ptr, d_node, d_dist, d_nh, cap, nh_bytes,
+                                  stream, out_total, out_solved);
 }
 
 int openr_spf_whatif_delta(openr_spf_ctx* ctx, const uint32_t* links, uint32_t n_links, const uint32_t* sources,
                            uint32_t n_sources, uint32_t flags, uint32_t* changed, openr_spf_whatif_delta_t* delta,
                            uint64_t* out_solved) {
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (!delta || !delta->ptr) return fail(OPENR_SPF_EINVAL, "null delta or delta->ptr");
-  if ((n_links && !links) || (n_sources && !sources) || (n_links && n_sources && !changed))
-    return fail(OPENR_SPF_EINVAL, "null links, sources or changed");
-  if (delta->cap && (!delta->node || !delta->dist || !delta->nh))
-    return fail(OPENR_SPF_EINVAL, "null delta->node, dist or nh");
-  for (uint32_t i = 0; i < n_sources; ++i)
-    if (sources[i] >= ctx->V) return fail(OPENR_SPF_EINVAL, "source %u out of range (V=%u)", sources[i], ctx->V);
-  for (uint32_t i = 0; i < n_links; ++i)
-    if (links[i] >= ctx->L) return fail(OPENR_SPF_EINVAL, "link %u out of range (L=%u)", links[i], ctx->L);
-  const auto t0 = std::chrono::steady_clock::now();
-  const uint32_t nhb = delta->nh_bytes;
-  // links split in contiguous blocks across the devices (openr_spf_whatif); each device's
-  // CSR is appended to the caller's at the running total
-  const uint32_t nd = (uint32_t)ctx->devs.size();
-  const uint32_t per = (n_links + nd - 1) / std::max<uint32_t>(nd, 1);
-  uint64_t solved_total = 0, at = 0;
-  bool over = false;
-  delta->ptr[0] = 0;
-  std::vector<uint64_t> ptr;
-  std::vector<uint32_t> idx;
-  for (uint32_t di = 0; di < nd; ++di) {
-    Device& d = ctx->devs[di];
-    const uint32_t b = std::min(n_links, di * per), e = std::min(n_links, b + per), m = e - b;
-    if (!m || !n_sources) continue;
-    const size_t mu = (size_t)m * n_sources;
-    HIP_TRY(hipSetDevice(d.ordinal));
-    HIP_TRY(d.win_links.reserve(m));
-    HIP_TRY(d.win_src.reserve(n_sources));
-    HIP_TRY(d.wchanged.reserve(mu));
-    HIP_TRY(d.dlo_ptr.reserve(mu + 1));
-    HIP_TRY(hipMemcpyAsync(d.win_links.p, links + b, m * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
-    HIP_TRY(hipMemcpyAsync(d.win_src.p, sources, n_sources * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
-    // the device's entries land in library buffers sized to the room left in the caller's
-    const uint64_t room = delta->cap > at ? delta->cap - at : 0;
-    HIP_TRY(d.dlo_node.reserve(std::max<uint64_t>(room, 1)));
-    HIP_TRY(d.dlo_dist.reserve(std::max<uint64_t>(room, 1)));
-    HIP_TRY(d.dlo_nh.reserve(std::max<uint64_t>(room * nhb, 1)));
-    uint64_t total = 0, solved = 0;
-    int rc = whatif_delta_on_device(ctx, d, d.win_links.p, m, d.win_src.p, n_sources, flags, d.wchanged.p,
-                                    reinterpret_cast<uint64_t*>(d.dlo_ptr.p), d.dlo_node.p, d.dlo_dist.p, d.dlo_nh.p,
-                                    room, nhb, d.stream, &total, &solved);
-    if (rc && rc != OPENR_SPF_E2BIG) return rc;
-    over |= rc == OPENR_SPF_E2BIG;
-    solved_total += solved;
-    ptr.resize(mu + 1);
-    HIP_TRY(hipMemcpyAsync(changed + (size_t)b * n_sources, d.wchanged.p, mu * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                           d.stream));
-    HIP_TRY(hipMemcpyAsync(ptr.data(), d.dlo_ptr.p, (mu + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
-    const bool fits = !over && total <= room;
-    if (fits && total) {
-      HIP_TRY(hipMemcpyAsync(delta->node + at, d.dlo_node.p, total * 4u, hipMemcpyDeviceToHost, d.stream));
-      HIP_TRY(hipMemcpyAsync(delta->dist + at, d.dlo_dist.p, total * 8u, hipMemcpyDeviceToHost, d.stream));
-      HIP_TRY(hipMemcpyAsync(delta->nh + at * nhb, d.dlo_nh.p, total * nhb, hipMemcpyDeviceToHost, d.stream));
-    }
-    HIP_TRY(hipStreamSynchronize(d.stream));
-    for (size_t u = 0; u < mu; ++u) {
-      const size_t gu = (size_t)b * n_sources + u;
-      delta->ptr[gu + 1] = at + ptr[u + 1];
-      const uint32_t c = (uint32_t)(ptr[u + 1] - ptr[u]);
-      if (!fits || c < 2) continue;
-      // each unit's nodes ascending (the device keeps the repair's order)
-      const uint64_t o = at + ptr[u];
-      bool sorted = true;
-      for (uint32_t k = 1; k < c && sorted; ++k) sorted = delta->node[o + k - 1] < delta->node[o + k];
-      if (sorted) continue;
-      idx.resize(c);
-      for (uint32_t k = 0; k < c; ++k) idx[k] = k;
-      std::sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return delta->node[o + x] < delta->node[o + y]; });
-      std::vector<uint32_t> tn(c);
-      std::vector<uint64_t> td(c);
-      std::vector<uint8_t> th((size_t)c * nhb);
-      for (uint32_t k = 0; k < c; ++k) {
-        tn[k] = delta->node[o + idx[k]];
-        td[k] = delta->dist[o + idx[k]];
-        std::memcpy(&th[(size_t)k * nhb], delta->nh + (o + idx[k]) * nhb, nhb);
-      }
-      std::memcpy(delta->node + o, tn.data(), c * 4u);
-      std::memcpy(delta->dist + o, td.data(), c * 8u);
-      std::memcpy(delta->nh + o * nhb, th.data(), (size_t)c * nhb);
-    }
-    at += total;
-  }
-  ctx->stats.last_batch_ms =
-      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (out_solved) *out_solved = solved_total;
-  if (over || at > delta->cap)
-    return fail(OPENR_SPF_E2BIG, "delta needs %llu entries, cap %llu (ptr and changed are filled, entries are not)",
-                (unsigned long long)at, (unsigned long long)delta->cap);
-  return OPENR_SPF_OK;
+  WhatifUnits hu;
+  hu.links = links;
+  hu.n = n_links;
+  return whatif_delta_host(ctx, hu, sources, n_sources, flags, changed, delta, out_solved);
+}
+
+int openr_spf_whatif_sets_delta(openr_spf_ctx* ctx, const uint32_t* set_ptr, const uint32_t* set_links,
+                                uint32_t n_sets, const uint32_t* sources, uint32_t n_sources, uint32_t flags,
+                                uint32_t* changed, openr_spf_whatif_delta_t* delta, uint64_t* out_solved) {
+  clear_launch_trace();
+  if (n_sets && !set_ptr) return fail(OPENR_SPF_EINVAL, "null set_ptr");
+  return whatif_delta_host(ctx, host_sets(set_ptr, set_links, n_sets), sources, n_sources, flags, changed, delta,
+                           out_solved);
 }
 
 int openr_spf_ksp2(openr_spf_ctx* ctx, const uint32_t* src, const uint32_t* dst, uint32_t n_pairs,

@@ -247,6 +247,17 @@ uint32_t rounds_lds_bytes(uint32_t V, uint32_t L, bool has_ignore, int nh_mode, 
 hipError_t launch_whatif_filter(const DevGraph& g, const uint32_t* links, uint32_t n_links, const uint32_t* sources,
                                 uint32_t n_src, const uint64_t* base_tight, uint32_t* changed, uint32_t* wsrc,
                                 uint32_t* wlink, uint32_t* wunit, uint32_t* wcount, int num_cus, hipStream_t s);
+// Link-set form (node failures, shared-risk groups): unit u = i * n_src + j fails every link
+// of set i = set_links[set_ptr[i], set_ptr[i + 1]) for sources[j]. changed[u] = 0 for every
+// unit; a unit is affected iff some link of its set has a tight edge in base_tight[j] (null
+// base_tight: iff some link of its set is a link of the graph). Affected units are appended
+// source-major to (wsrc, wunit, wbeg = set_ptr[i], wend = set_ptr[i + 1]), *wcount of them:
+// the re-solves run with ign_ptr = wbeg, ign_end = wend, ign_links = set_links. Slices are
+// clamped to set_links' n_set_links entries (a malformed device CSR reads nothing past it).
+hipError_t launch_whatif_set_filter(const DevGraph& g, const uint32_t* set_ptr, const uint32_t* set_links,
+                                    uint32_t n_sets, uint32_t n_set_links, const uint32_t* sources,
+                                    uint32_t n_src, const uint64_t* base_tight, uint32_t* changed, uint32_t* wsrc, uint32_t* wunit,
+                                    uint32_t* wbeg, uint32_t* wend, uint32_t* wcount, int num_cus, hipStream_t s);
 // changed[wunit[k]] = nodes whose dist / next-hop bytes differ from base row wunit[k] % n_src.
 // With dl.node: also the unit's changed nodes and their new rows (WhatifDelta).
 hipError_t launch_rows_compare(uint32_t n, uint32_t V, uint32_t nb, const uint64_t* dist, const uint8_t* nh,

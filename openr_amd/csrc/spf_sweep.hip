@@ -64,6 +64,65 @@ __global__ __launch_bounds__(256) void whatif_filter(const uint2* ledge, uint32_
   }
 }
 
+// Set form of the filter (openr_spf_whatif_sets): unit u = i * n_src + j fails every link of
+// set i = set_links[set_ptr[i], set_ptr[i + 1]) at once for sources[j]. The argument of the
+// header comment holds for a set: dist and nh depend on tight edges only, so a set none of
+// whose links carries a base-tight edge (either direction) changes nothing. With
+// base_tight == nullptr (exact-order plans with zero / wrapped metrics) a unit is affected
+// iff some link of its set is a link of the graph, whatif_filter's rule. Link ids >= L and
+// unused ids are skipped, as load_ignore skips them; an empty set is never affected.
+// One thread per unit, threads in source-major order (t = j * n_sets + i): a wave's units
+// and, as far as workgroups append in launch order, consecutive list entries share a source,
+// so the seeded re-solves of neighbouring entries re-read the same base rows from L2. The
+// list points each unit at its set (wbeg / wend index set_links; no set is copied).
+// The loop over a set's links has a lane-dependent trip count (a wave can straddle sets of
+// different sizes): every wave collective stays outside it.
+__global__ __launch_bounds__(256) void whatif_set_filter(const uint2* ledge, uint32_t L, uint32_t tight_words,
+                                                         const uint32_t* set_ptr, const uint32_t* set_links,
+                                                         uint32_t n_sets, uint32_t n_set_links,
+                                                         const uint32_t* sources, uint32_t n_src,
+                                                         const uint64_t* base_tight, uint32_t* changed,
+                                                         uint32_t* wsrc, uint32_t* wunit, uint32_t* wbeg,
+                                                         uint32_t* wend, uint32_t* wcount) {
+  const uint64_t total = (uint64_t)n_sets * n_src;
+  for (uint64_t t0 = (uint64_t)blockIdx.x * 256u; t0 < total; t0 += (uint64_t)gridDim.x * 256u) {
+    const uint64_t t = t0 + threadIdx.x;
+    bool hit = false;
+    uint32_t j = 0, b = 0, e = 0;
+    uint64_t u = 0;
+    if (t < total) {
+      j = (uint32_t)(t / n_sets);
+      const uint32_t i = (uint32_t)(t - (uint64_t)j * n_sets);
+      u = (uint64_t)i * n_src + j;
+      changed[u] = 0;
+      b = min(set_ptr[i], n_set_links);  // a slice never reaches past set_links
+      e = min(max(set_ptr[i + 1], b), n_set_links);
+      const uint64_t* trow = base_tight ? base_tight + (size_t)j * tight_words : nullptr;
+      for (uint32_t k = b; k < e && !hit; ++k) {
+        const uint32_t l = set_links[k];
+        if (l >= L) continue;
+        const uint2 ee = ledge[l];
+        if (ee.x == UINT32_MAX) continue;
+        hit = !trow || ((trow[ee.x >> 6] >> (ee.x & 63u)) & 1ull) || ((trow[ee.y >> 6] >> (ee.y & 63u)) & 1ull);
+      }
+    }
+    const unsigned long long m = __ballot(hit);
+    if (!m) continue;
+    const uint32_t lane = __lane_id();
+    const uint32_t leader = (uint32_t)(__ffsll((long long)m) - 1);
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(wcount, (uint32_t)__popcll(m));
+    base = __shfl(base, (int)leader);
+    if (hit) {
+      const uint32_t k = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      wsrc[k] = sources[j];
+      wunit[k] = (uint32_t)u;
+      wbeg[k] = b;
+      wend[k] = e;
+    }
+  }
+}
+
 // changed[wunit[k]] = number of nodes whose distance or next-hop bytes differ from the
 // base row of source j = wunit[k] % n_src. One workgroup per solved unit.
 __global__ __launch_bounds__(256) void rows_compare(uint32_t n, uint32_t V, uint32_t nb, const uint64_t* dist,
@@ -1414,6 +1473,20 @@ hipError_t launch_whatif_filter(const DevGraph& g, const uint32_t* links, uint32
   hipLaunchKernelGGL(whatif_filter, dim3(grid_for(total, 256u, num_cus)), dim3(256), 0, s, g.ledge, g.L,
                      (g.E + 63u) / 64u, links, n_links, sources, n_src, base_tight, changed, wsrc, wlink, wunit,
                      wcount);
+  return hipGetLastError();
+}
+
+hipError_t launch_whatif_set_filter(const DevGraph& g, const uint32_t* set_ptr, const uint32_t* set_links,
+                                    uint32_t n_sets, uint32_t n_set_links, const uint32_t* sources,
+                                    uint32_t n_src, const uint64_t* base_tight, uint32_t* changed, uint32_t* wsrc, uint32_t* wunit,
+                                    uint32_t* wbeg, uint32_t* wend, uint32_t* wcount, int num_cus, hipStream_t s) {
+  hipError_t err = hipMemsetAsync(wcount, 0, sizeof(uint32_t), s);
+  if (err != hipSuccess) return err;
+  const uint64_t total = (uint64_t)n_sets * n_src;
+  if (!total) return hipSuccess;
+  hipLaunchKernelGGL(whatif_set_filter, dim3(grid_for(total, 256u, num_cus)), dim3(256), 0, s, g.ledge, g.L,
+                     (g.E + 63u) / 64u, set_ptr, set_links, n_sets, n_set_links, sources, n_src, base_tight, changed, wsrc, wunit,
+                     wbeg, wend, wcount);
   return hipGetLastError();
 }
 

@@ -46,6 +46,10 @@ EXPORTS = (
     "openr_spf_whatif_device",
     "openr_spf_whatif_delta",
     "openr_spf_whatif_delta_device",
+    "openr_spf_whatif_sets",
+    "openr_spf_whatif_sets_device",
+    "openr_spf_whatif_sets_delta",
+    "openr_spf_whatif_sets_delta_device",
     "openr_spf_ksp2",
     "openr_spf_ksp2_device",
     "openr_spf_host_alloc",
@@ -153,6 +157,13 @@ def load_library():
     l.openr_spf_whatif_delta.argtypes = [vp, vp, u32, vp, u32, u32, vp, P(WhatifDelta), P(ctypes.c_uint64)]
     l.openr_spf_whatif_delta_device.argtypes = [vp, ctypes.c_int, vp, u32, vp, u32, u32, vp, vp, vp, vp, vp,
                                                 ctypes.c_uint64, u32, vp, P(ctypes.c_uint64), P(ctypes.c_uint64)]
+    l.openr_spf_whatif_sets.argtypes = [vp, vp, vp, u32, vp, u32, u32, vp, P(ctypes.c_uint64)]
+    l.openr_spf_whatif_sets_device.argtypes = [vp, ctypes.c_int, vp, vp, u32, u32, vp, u32, u32, vp, vp,
+                                               P(ctypes.c_uint64)]
+    l.openr_spf_whatif_sets_delta.argtypes = [vp, vp, vp, u32, vp, u32, u32, vp, P(WhatifDelta), P(ctypes.c_uint64)]
+    l.openr_spf_whatif_sets_delta_device.argtypes = [vp, ctypes.c_int, vp, vp, u32, u32, vp, u32, u32, vp, vp, vp, vp,
+                                                     vp, ctypes.c_uint64, u32, vp, P(ctypes.c_uint64),
+                                                     P(ctypes.c_uint64)]
     l.openr_spf_ksp2.argtypes = [vp, vp, vp, u32, u32, vp, vp]
     l.openr_spf_ksp2_device.argtypes = [vp, ctypes.c_int, vp, u32, vp, vp, u32, u32, vp, vp, vp]
     l.openr_spf_host_alloc.argtypes = [ctypes.c_size_t, P(vp)]
@@ -356,6 +367,78 @@ class SpfEngine:
                                                      n_sources, flags, vp(d_changed), vp(d_ptr), vp(d_node or None),
                                                      vp(d_dist or None), vp(d_nh or None), cap, nh_bytes,
                                                      vp(stream or None), ctypes.byref(total), ctypes.byref(solved))
+        if not (allow_overflow and rc == E2BIG):
+            _check(rc)
+        return int(total.value), int(solved.value)
+
+    def whatif_sets(self, sets: Sequence[Sequence[int]], sources: Sequence[int], use_link_metric: bool = True
+                    ) -> Tuple[np.ndarray, int]:
+        """Link-set failure sweep (node failures, shared-risk groups; openr_spf_whatif_sets):
+        (changed[n_sets, n_sources] u32, SPFs run). Unit (i, j) fails every link of sets[i]."""
+        n = len(sets)
+        sp, sl = _ignore_arrays(sets, n)
+        src = np.ascontiguousarray(sources, dtype=np.uint32)
+        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
+        solved = ctypes.c_uint64()
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        _check(self._lib.openr_spf_whatif_sets(self._ctx, _p(sp), _p(sl), n, _p(src), src.shape[0], flags,
+                                               _p(changed), ctypes.byref(solved)))
+        return changed, int(solved.value)
+
+    def whatif_sets_device(self, d_set_ptr: int, d_set_links: int, n_sets: int, n_set_links: int, d_sources: int,
+                           n_sources: int, d_changed: int, use_link_metric: bool = True, stream: int = 0,
+                           device_index: int = 0) -> int:
+        """Device-pointer form (d_set_ptr [n_sets + 1], d_set_links [n_set_links]); returns
+        the number of SPFs run."""
+        vp = ctypes.c_void_p
+        solved = ctypes.c_uint64()
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        _check(self._lib.openr_spf_whatif_sets_device(self._ctx, device_index, vp(d_set_ptr or None),
+                                                      vp(d_set_links or None), n_sets, n_set_links, vp(d_sources),
+                                                      n_sources, flags, vp(d_changed), vp(stream or None),
+                                                      ctypes.byref(solved)))
+        return int(solved.value)
+
+    def whatif_sets_delta(self, sets: Sequence[Sequence[int]], sources: Sequence[int], use_link_metric: bool = True,
+                          cap: Optional[int] = None, nh_bytes: Optional[int] = None):
+        """Link-set failure sweep with each unit's delta (openr_spf_whatif_sets_delta): the
+        return shape of whatif_delta, unit u = i * n_sources + j failing every link of sets[i].
+        cap None: sized from a count-only pass."""
+        n = len(sets)
+        sp, sl = _ignore_arrays(sets, n)
+        src = np.ascontiguousarray(sources, dtype=np.uint32)
+        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
+        if cap is None:
+            changed, _ = self.whatif_sets(sets, src, use_link_metric)
+            cap = int(changed.sum(dtype=np.uint64))
+        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
+        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
+        node = np.zeros(max(cap, 1), dtype=np.uint32)
+        dist = np.zeros(max(cap, 1), dtype=np.uint64)
+        nh = np.zeros((max(cap, 1), nb), dtype=np.uint8)
+        d = WhatifDelta(_p(ptr), _p(node), _p(dist), _p(nh), cap, nb)
+        solved = ctypes.c_uint64()
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        _check(self._lib.openr_spf_whatif_sets_delta(self._ctx, _p(sp), _p(sl), n, _p(src), src.shape[0], flags,
+                                                     _p(changed), ctypes.byref(d), ctypes.byref(solved)))
+        k = int(ptr[-1])
+        return changed, ptr, node[:k], dist[:k], nh[:k], int(solved.value)
+
+    def whatif_sets_delta_device(self, d_set_ptr: int, d_set_links: int, n_sets: int, n_set_links: int,
+                                 d_sources: int, n_sources: int, d_changed: int, d_ptr: int, d_node: int,
+                                 d_dist: int, d_nh: int, cap: int, nh_bytes: int, use_link_metric: bool = True,
+                                 stream: int = 0, device_index: int = 0,
+                                 allow_overflow: bool = False) -> Tuple[int, int]:
+        """Device-pointer form: (total entries, SPFs run). d_ptr [n_units + 1] u64 CSR; unit
+        u's entries are [ptr[u], ptr[u + 1]) in the re-solve's order."""
+        vp = ctypes.c_void_p
+        total = ctypes.c_uint64()
+        solved = ctypes.c_uint64()
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        rc = self._lib.openr_spf_whatif_sets_delta_device(
+            self._ctx, device_index, vp(d_set_ptr or None), vp(d_set_links or None), n_sets, n_set_links,
+            vp(d_sources), n_sources, flags, vp(d_changed), vp(d_ptr), vp(d_node or None), vp(d_dist or None),
+            vp(d_nh or None), cap, nh_bytes, vp(stream or None), ctypes.byref(total), ctypes.byref(solved))
         if not (allow_overflow and rc == E2BIG):
             _check(rc)
         return int(total.value), int(solved.value)

@@ -462,3 +462,29 @@ def from_adj_map(adj_map: Dict[int, Sequence], name_fmt: str = "{}") -> CsrGraph
                                   (node << 16) + adj))
         dbs.append(AdjacencyDatabase(name_fmt.format(node), adjs, False, node))
     return build_csr(dbs)
+
+
+def node_failure_sets(g: CsrGraph, nodes: Optional[Sequence[int]] = None) -> List[List[int]]:
+    """Link sets of node failures for ``SpfEngine.whatif_sets``: for each node (all of them
+    when ``nodes`` is None) the sorted distinct link ids of its CSR row, i.e. every link
+    that goes down with the router. A node without links gives an empty set."""
+    ids = range(g.num_nodes) if nodes is None else [int(u) for u in nodes]
+    out = []
+    for u in ids:
+        if not 0 <= u < g.num_nodes:
+            raise ValueError(f"node {u} out of range (V={g.num_nodes})")
+        out.append(sorted(set(g.link_id[g.row_ptr[u] : g.row_ptr[u + 1]].tolist())))
+    return out
+
+
+def srlg_sets(g: CsrGraph, groups: Iterable[Iterable[int]]) -> List[List[int]]:
+    """Caller-given shared-risk link groups as link sets for ``SpfEngine.whatif_sets``:
+    every group validated (link ids in [0, num_links)), de-duplicated and sorted."""
+    out = []
+    for k, grp in enumerate(groups):
+        links = sorted(set(int(l) for l in grp))
+        if links and not (0 <= links[0] and links[-1] < g.num_links):
+            bad = links[0] if links[0] < 0 else links[-1]
+            raise ValueError(f"group {k}: link {bad} out of range (L={g.num_links})")
+        out.append(links)
+    return out
