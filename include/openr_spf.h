@@ -24,6 +24,11 @@
  *                              new distance and next-hop bits
  *   openr_spf_whatif_sets      the sweep with a set of links per unit (node failures,
  *                              shared-risk link groups); _sets_delta adds the delta
+ *   openr_spf_routes           SpfSolver::getMinCostNodes + the shortest-path half of
+ *                              getNextHopsWithMetric (Decision.cpp:1094-1167) over prefix
+ *                              groups, for a batch of sources
+ *   openr_spf_whatif_routes    the link-set sweep resolved to routes: per (failure set,
+ *                              source) the groups whose route changed, with the new route
  *   openr_spf_ksp2             LinkState::getKthPaths(src, dst, 1 and 2) (LinkState.cpp:762-791)
  *                              for a batch of pairs, paths traced on the device
  *   openr_spf_patch_graph      attribute-only mirror updates (metric, Link::isUp, node
@@ -313,6 +318,90 @@ int openr_spf_whatif_sets_delta_device(openr_spf_ctx* ctx, int device_index,
                                        uint32_t* d_node, uint64_t* d_dist, uint8_t* d_nh,
                                        uint64_t cap, uint32_t nh_bytes, void* stream,
                                        uint64_t* out_total, uint64_t* out_solved);
+
+/* A table of prefix groups (CSR). A prefix is advertised by a set of nodes (anycast); after
+   SpfSolver::selectBestRoutes its best advertisers are the group. Group k is
+   group_nodes[group_ptr[k] .. group_ptr[k + 1]), node ids < V strictly ascending inside a
+   group (no duplicates). Empty groups are allowed; a node may sit in any number of groups. */
+typedef struct {
+  uint32_t n_groups;
+  const uint32_t* group_ptr;    /* [n_groups + 1] */
+  const uint32_t* group_nodes;  /* [group_ptr[n_groups]] */
+} openr_spf_groups_t;
+
+/* Best-path selection over prefix groups for a batch of sources: SpfSolver::getMinCostNodes
+   plus the shortest-path half of getNextHopsWithMetric (Decision.cpp:1094-1167) on the rows
+   of openr_spf_solve. For source i and group k (G = n_groups):
+     metric[i][k]  the minimum of dist[v] over the members with dist[v] != UINT64_MAX;
+                   UINT64_MAX if there is none (an empty group is unreachable)
+     nh[i][k][b]   the OR of nh[v] over the members at that minimum, nh_bytes bytes in
+                   openr_spf_solve's layout, zero past the graph's width, all zero when
+                   metric is UINT64_MAX (nullable; nh_bytes >= openr_spf_nh_bytes)
+     n_best[i][k]  the number of members at the minimum, 0 when unreachable (nullable)
+   A group that contains the source has metric 0 and an empty nh, as getMinCostNodes gives.
+   With OPENR_SPF_USE_LINK_METRIC a graph with a usable metric outside [1, 2^31-1] returns
+   OPENR_SPF_ENOTSUP, as openr_spf_ksp2 does (a reached node can carry UINT64_MAX there, and
+   the rule would misread it); the hop-count form is always allowed. A member >= V, a
+   group_ptr that does not ascend or a group that is not strictly ascending is
+   OPENR_SPF_EINVAL. The sources are solved into library scratch (in chunks when n x V rows
+   exceed the what-if chunk budget) and reduced on the device; they are split in contiguous
+   blocks across the context's devices. */
+int openr_spf_routes(openr_spf_ctx* ctx, const uint32_t* sources, uint32_t n, uint32_t flags,
+                     const openr_spf_groups_t* groups, uint64_t* metric, uint8_t* nh, uint32_t nh_bytes,
+                     uint32_t* n_best);
+
+/* Device-buffer form (every pointer device memory; d_group_nodes has n_group_nodes entries;
+   d_nh / d_n_best may be NULL). The group table is not validated: a slice is clamped to
+   n_group_nodes and a member >= V counts as unreachable. Asynchronous on `stream`. */
+int openr_spf_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_sources, uint32_t n,
+                            uint32_t flags, const uint32_t* d_group_ptr, const uint32_t* d_group_nodes,
+                            uint32_t n_groups, uint32_t n_group_nodes, uint64_t* d_metric, uint8_t* d_nh,
+                            uint32_t nh_bytes, uint32_t* d_n_best, void* stream);
+
+/* Route-level what-if sweep: which routes move when a router or a shared-risk group fails,
+   i.e. what Decision's route rebuild (getMinCostNodes / getNextHopsWithMetric,
+   Decision.cpp:1094-1167) yields on LinkState::runSpf(sources[j], useLinkMetric, set i)
+   (LinkState.cpp:808-882) where it differs from the no-failure routes of sources[j].
+   Failure units are link sets exactly as in openr_spf_whatif_sets (single links are
+   singleton sets); its validation and the meaning of *out_solved hold here. The route of a
+   group changed iff its metric or nh differs from the no-failure route of the same source; a
+   move of n_best alone is not a change (the RIB entry is identical), n_best is still
+   reported with each changed route. changed_routes [n_sets][n_sources] counts them.
+   delta (nullable: counts only) is a CSR over units u = i * n_sources + j like the node
+   delta: unit u's entries are [ptr[u], ptr[u + 1]), group ids ascending, metric UINT64_MAX
+   for a route the failure removes, nh in openr_spf_routes' layout (nh_bytes >= the graph's
+   width, zero past it). OPENR_SPF_E2BIG means sum(changed_routes) > cap and nothing else:
+   ptr and changed_routes are filled, the entries are not. The node delta the pass reads is
+   held in library scratch that grows as needed. Errors for groups and metrics as in
+   openr_spf_routes. Sets are split in contiguous blocks across the context's devices. */
+typedef struct {
+  uint64_t* ptr;     /* [n_sets * n_sources + 1] */
+  uint32_t* group;   /* [cap] group ids, ascending inside a unit */
+  uint64_t* metric;  /* [cap] new metric, UINT64_MAX = route lost */
+  uint8_t* nh;       /* [cap][nh_bytes] */
+  uint32_t* n_best;  /* [cap], nullable */
+  uint64_t cap;      /* entries the caller allocated */
+  uint32_t nh_bytes; /* bytes per next-hop entry */
+} openr_spf_whatif_routes_t;
+int openr_spf_whatif_routes(openr_spf_ctx* ctx, const uint32_t* set_ptr, const uint32_t* set_links, uint32_t n_sets,
+                            const uint32_t* sources, uint32_t n_sources, uint32_t flags,
+                            const openr_spf_groups_t* groups, uint32_t* changed_routes,
+                            openr_spf_whatif_routes_t* delta, uint64_t* out_solved);
+
+/* Device-buffer form (every buffer device memory; sets as in openr_spf_whatif_sets_device,
+   groups as in openr_spf_routes_device, not validated): d_changed_routes [n_sets][n_sources],
+   d_ptr [n_units + 1], each unit's entries in the order the kernel found them (not sorted);
+   d_n_best may be NULL. *out_total (host, nullable) = sum(changed_routes). d_ptr and
+   d_changed_routes are always filled; when the total exceeds cap the entries are not, and
+   the call returns OPENR_SPF_E2BIG (cap 0: counts and ptr only). Synchronizes `stream`. */
+int openr_spf_whatif_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_set_ptr,
+                                   const uint32_t* d_set_links, uint32_t n_sets, uint32_t n_set_links,
+                                   const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                                   const uint32_t* d_group_ptr, const uint32_t* d_group_nodes, uint32_t n_groups,
+                                   uint32_t n_group_nodes, uint32_t* d_changed_routes, uint64_t* d_ptr,
+                                   uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh, uint32_t* d_n_best,
+                                   uint64_t cap, uint32_t nh_bytes, void* stream, uint64_t* out_total,
+                                   uint64_t* out_solved);
 
 /* LinkState::getKthPaths(src[i], dst[i], 1) and (.., 2) (LinkState.cpp:762-791, with
    traceOnePath :398-419) for a batch of pairs, traced on the device. Per pair, tok1 /

@@ -111,6 +111,13 @@ struct Device {
   DevBuf<unsigned long long> dlo_ptr, dlo_dist;
   DevBuf<uint32_t> dlo_node;
   DevBuf<uint8_t> dlo_nh;
+  // route-level calls (spf_routes.hip): the sweep's node delta in CSR form, the base routes,
+  // the inverse map node -> groups, the per-workgroup overlay / bitmap slices when they are
+  // not in LDS, and the host forms' group table and outputs before they are copied out
+  DevBuf<unsigned long long> rt_nptr, rt_ndist, rt_bmetric, rt_iptr, rt_tsum, rt_optr, rt_ometric;
+  DevBuf<uint32_t> rt_nchanged, rt_nnode, rt_inv, rt_icnt, rt_icur, rt_large, rt_ovl, rt_bm;
+  DevBuf<uint32_t> rt_gptr, rt_gnodes, rt_ochanged, rt_ogroup, rt_onbest;
+  DevBuf<uint8_t> rt_nnh, rt_bnh, rt_onh;
   // incremental updates: patch records, the last patch's delta edges, refresh work list,
   // host-form refresh rows
   DevBuf<PatchRec> precs;
@@ -1109,7 +1116,8 @@ hipError_t whatif_units_on_device(openr_spf_ctx* ctx, Device& d, const Plan& bp,
 // Synchronizes s. *total = sum(changed); OPENR_SPF_E2BIG when it exceeds cap.
 int whatif_delta_on_device(openr_spf_ctx* ctx, Device& d, const WhatifUnits& un, const uint32_t* d_sources, uint32_t n_src, uint32_t flags, uint32_t* d_changed,
                            uint64_t* d_ptr, uint32_t* d_node, unsigned long long* d_dist, uint8_t* d_nh, uint64_t cap,
-                           uint32_t nhb, hipStream_t s, uint64_t* total, uint64_t* solved_out) {
+                           uint32_t nhb, hipStream_t s, uint64_t* total, uint64_t* solved_out,
+                           uint64_t* pool_need = nullptr) {
   const uint32_t nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
   if (nhb < nb) return fail(OPENR_SPF_EINVAL, "nh_bytes %u below the graph's next-hop width %u", nhb, nb);
   Plan bp, ip;
@@ -1152,6 +1160,7 @@ int whatif_delta_on_device(openr_spf_ctx* ctx, Device& d, const WhatifUnits& un,
   HIP_TRY(hipStreamSynchronize(s));
   *total = tu[0];
   *solved_out = (uint64_t)solved + n_src;
+  if (pool_need) *pool_need = tu[1];  // scratch slots the sweep asked for (the route pass sizes its rerun from it)
   ctx->stats.spf_runs += *solved_out;
   ctx->stats.batches += 1;
   if (tu[1] > want)
@@ -1417,6 +1426,374 @@ WhatifUnits device_sets(const uint32_t* d_set_ptr, const uint32_t* d_set_links, 
   return un;
 }
 
+// ---- route-level calls (spf_routes.hip) ---------------------------------------------------
+
+// A group table in device memory: group k = nodes[ptr[k], ptr[k + 1]), m entries in nodes.
+struct DevGroups {
+  const uint32_t* ptr = nullptr;
+  const uint32_t* nodes = nullptr;
+  uint32_t n = 0, m = 0;
+};
+
+// The rule "metric = min over members with dist != UINT64_MAX" reads UINT64_MAX as "not in
+// the SpfResult"; with zero or wrapped metrics a reached node can carry it (openr_spf.h).
+int check_routes_metric(const openr_spf_ctx* ctx, uint32_t flags) {
+  if ((flags & OPENR_SPF_USE_LINK_METRIC) && !ctx->metric_ok)
+    return fail(OPENR_SPF_ENOTSUP, "routes need usable metrics in [1, 2^31-1] under link metric (hop-count form is allowed)");
+  return OPENR_SPF_OK;
+}
+
+// Group-table checks of the host forms (the device forms do not check).
+int check_groups_host(const openr_spf_ctx* ctx, const openr_spf_groups_t* g) {
+  if (!g) return fail(OPENR_SPF_EINVAL, "null groups");
+  if (!g->n_groups) return OPENR_SPF_OK;
+  if (!g->group_ptr) return fail(OPENR_SPF_EINVAL, "null group_ptr");
+  for (uint32_t k = 0; k < g->n_groups; ++k)
+    if (g->group_ptr[k + 1] < g->group_ptr[k])
+      return fail(OPENR_SPF_EINVAL, "group_ptr does not ascend at group %u", k);
+  if (g->group_ptr[g->n_groups] && !g->group_nodes) return fail(OPENR_SPF_EINVAL, "null group_nodes");
+  for (uint32_t k = 0; k < g->n_groups; ++k)
+    for (uint32_t m = g->group_ptr[k]; m < g->group_ptr[k + 1]; ++m) {
+      if (g->group_nodes[m] >= ctx->V)
+        return fail(OPENR_SPF_EINVAL, "group %u: node %u out of range (V=%u)", k, g->group_nodes[m], ctx->V);
+      if (m > g->group_ptr[k] && g->group_nodes[m] <= g->group_nodes[m - 1])
+        return fail(OPENR_SPF_EINVAL, "group %u is not strictly ascending", k);
+    }
+  return OPENR_SPF_OK;
+}
+
+int upload_groups(Device& d, const openr_spf_groups_t* g, DevGroups* out) {
+  *out = DevGroups{};
+  out->n = g->n_groups;
+  if (!g->n_groups) return OPENR_SPF_OK;
+  out->m = g->group_ptr[g->n_groups];
+  HIP_TRY(d.rt_gptr.reserve((size_t)out->n + 1u));
+  HIP_TRY(d.rt_gnodes.reserve(std::max<uint32_t>(out->m, 1u)));
+  HIP_TRY(hipMemcpyAsync(d.rt_gptr.p, g->group_ptr, ((size_t)out->n + 1u) * sizeof(uint32_t), hipMemcpyHostToDevice,
+                         d.stream));
+  if (out->m)
+    HIP_TRY(hipMemcpyAsync(d.rt_gnodes.p, g->group_nodes, (size_t)out->m * sizeof(uint32_t), hipMemcpyHostToDevice,
+                           d.stream));
+  out->ptr = d.rt_gptr.p;
+  out->nodes = d.rt_gnodes.p;
+  return OPENR_SPF_OK;
+}
+
+// openr_spf_routes[_device] on one device: the sources solved through the ordinary launcher
+// into library scratch (the what-if base rows' buffers), a chunk of rows at a time when
+// n x V rows exceed the what-if chunk budget, each chunk reduced to its routes. Enqueues
+// only; OPENR_SPF_ROUTES_CHUNK (tests) forces a chunk size in rows.
+int routes_on_device(openr_spf_ctx* ctx, Device& d, const uint32_t* d_sources, uint32_t n, uint32_t flags,
+                     const DevGroups& gr, uint64_t* d_metric, uint8_t* d_nh, uint32_t nhb, uint32_t* d_nbest,
+                     hipStream_t s) {
+  if (!n || !gr.n) return OPENR_SPF_OK;
+  Plan plan;
+  int rc = make_plan(ctx, flags & OPENR_SPF_USE_LINK_METRIC, false, &plan);
+  if (rc) return rc;
+  const uint32_t V = ctx->V;
+  const uint32_t nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
+  uint32_t chunk = (uint32_t)std::min<size_t>(n, std::max<size_t>(1, kWhatifChunkBytes / ((size_t)V * (8u + nb))));
+  if (const char* e = std::getenv("OPENR_SPF_ROUTES_CHUNK"))
+    if (std::atoi(e) > 0) chunk = std::min<uint32_t>(chunk, (uint32_t)std::atoi(e));
+  HIP_TRY(d.base_dist.reserve((size_t)chunk * V));
+  HIP_TRY(d.base_nh.reserve((size_t)chunk * V * nb));
+  HIP_TRY(d.ovf.reserve((size_t)chunk * ctx->nsl_max()));
+  HIP_TRY(d.rt_large.reserve(routes_reduce_scratch_words(gr.n)));
+  HIP_TRY(reserve_counters(d));
+  for (uint32_t c0 = 0; c0 < n; c0 += chunk) {
+    const uint32_t m = std::min(chunk, n - c0);
+    SolveArgs a{};
+    a.sources = d_sources + c0;
+    a.n = m;
+    a.dist = d.base_dist.p;
+    a.nh = d.base_nh.p;
+    a.nh_bytes = nb;
+    a.nh_bits = ctx->nh_bits;
+    a.ovf_list = d.ovf.p;
+    a.work = d.work.p;
+    HIP_TRY(launch(ctx, d, plan, a, s));
+    const size_t o = (size_t)c0 * gr.n;
+    HIP_TRY(launch_routes_reduce(m, V, gr.n, gr.m, gr.ptr, gr.nodes, d.base_dist.p, d.base_nh.p, nb, d_metric + o,
+                                 d_nh ? d_nh + o * nhb : nullptr, nhb, d_nbest ? d_nbest + o : nullptr, d.rt_large.p,
+                                 d.num_cus, s));
+  }
+  ctx->stats.spf_runs += n;
+  ctx->stats.batches += 1;
+  return OPENR_SPF_OK;
+}
+
+// openr_spf_whatif_routes[_device] on one device. The link-set sweep runs with the node
+// delta in device form into library scratch (whatif_delta_on_device: base rows stay
+// resident in base_dist / base_nh); then the base routes of every source, the inverse map
+// node -> groups, the count pass, the scan of the counts into d_ptr, the cap check and the
+// emit pass. The node delta's capacity is the library's own: an estimate first, and on
+// overflow the sweep is rerun with the total it reported, so OPENR_SPF_E2BIG only ever
+// means sum(changed_routes) > cap. Synchronizes s.
+int whatif_routes_on_device(openr_spf_ctx* ctx, Device& d, const WhatifUnits& un, const uint32_t* d_sources,
+                            uint32_t n_src, uint32_t flags, const DevGroups& gr, uint32_t* d_changed, uint64_t* d_ptr,
+                            uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh, uint32_t* d_nbest, uint64_t cap,
+                            uint32_t nhb, hipStream_t s, uint64_t* total, uint64_t* solved_out) {
+  const uint32_t V = ctx->V, G = gr.n;
+  const uint32_t nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
+  if (nhb < nb) return fail(OPENR_SPF_EINVAL, "nh_bytes %u below the graph's next-hop width %u", nhb, nb);
+  *total = 0;
+  *solved_out = 0;
+  const size_t units = (size_t)un.n * n_src;
+  unsigned long long* ptr = reinterpret_cast<unsigned long long*>(d_ptr);
+  if (!units) {
+    HIP_TRY(hipMemsetAsync(ptr, 0, sizeof(unsigned long long), s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return OPENR_SPF_OK;
+  }
+  // 1. the node sweep; a unit changes ~6 nodes on a WAN and V at the most
+  HIP_TRY(d.rt_nchanged.reserve(units));
+  HIP_TRY(d.rt_nptr.reserve(units + 1u));
+  uint64_t ncap = std::min<uint64_t>((uint64_t)units * V, std::max<uint64_t>((uint64_t)units * 16u, 1u << 20));
+  if (const char* e = std::getenv("OPENR_SPF_ROUTES_DELTA_CAP"))  // tests: start below the total (the rerun)
+    ncap = std::strtoull(e, nullptr, 10);
+  uint64_t ntotal = 0;
+  for (int attempt = 0;; ++attempt) {
+    HIP_TRY(d.rt_nnode.reserve(std::max<uint64_t>(ncap, 1)));
+    HIP_TRY(d.rt_ndist.reserve(std::max<uint64_t>(ncap, 1)));
+    HIP_TRY(d.rt_nnh.reserve(std::max<uint64_t>(ncap * nb, 1)));
+    const openr_spf_stats_t stats0 = ctx->stats;
+    uint64_t pool = 0;
+    const int rc = whatif_delta_on_device(ctx, d, un, d_sources, n_src, flags, d.rt_nchanged.p,
+                                          reinterpret_cast<uint64_t*>(d.rt_nptr.p), d.rt_nnode.p, d.rt_ndist.p,
+                                          d.rt_nnh.p, ncap, nb, s, &ntotal, solved_out, &pool);
+    if (rc == OPENR_SPF_OK) break;
+    if (rc != OPENR_SPF_E2BIG) return rc;
+    if (attempt == 2 || ntotal > (uint64_t)units * V)
+      return fail(OPENR_SPF_ENOMEM, "node delta of %llu entries did not fit library scratch",
+                  (unsigned long long)ntotal);
+    ctx->stats = stats0;  // the rerun counts once
+    ncap = std::max<uint64_t>(ntotal, pool / 2u + 1u);
+  }
+  // 2. base routes, inverse map
+  HIP_TRY(hipMemsetAsync(d_changed, 0, units * sizeof(uint32_t), s));
+  const size_t bg = (size_t)n_src * G;
+  HIP_TRY(d.rt_bmetric.reserve(std::max<size_t>(bg, 1)));
+  HIP_TRY(d.rt_bnh.reserve(std::max<size_t>(bg * nb, 1)));
+  HIP_TRY(d.rt_large.reserve(routes_reduce_scratch_words(G)));
+  HIP_TRY(launch_routes_reduce(n_src, V, G, gr.m, gr.ptr, gr.nodes, d.base_dist.p, d.base_nh.p, nb,
+                               reinterpret_cast<uint64_t*>(d.rt_bmetric.p), d.rt_bnh.p, nb, nullptr, d.rt_large.p,
+                               d.num_cus, s));
+  HIP_TRY(d.rt_icnt.reserve(V));
+  HIP_TRY(d.rt_icur.reserve(V));
+  HIP_TRY(d.rt_iptr.reserve((size_t)V + 1u));
+  HIP_TRY(d.rt_inv.reserve(std::max<uint32_t>(gr.m, 1u)));
+  HIP_TRY(d.rt_tsum.reserve(std::max<size_t>(units, V) / 4096u + 1u));
+  HIP_TRY(launch_routes_inverse(V, G, gr.m, gr.ptr, gr.nodes, d.rt_icnt.p, d.rt_icur.p, d.rt_tsum.p, d.rt_iptr.p,
+                                d.rt_inv.p, d.num_cus, s));
+  // 3. count pass, scan, cap check, emit pass
+  const RoutesSweepLayout lay = whatif_routes_layout(V, G, units, d.num_cus);
+  HIP_TRY(d.rt_ovl.reserve(std::max<size_t>(lay.ovl_words, 1)));
+  HIP_TRY(d.rt_bm.reserve(std::max<size_t>(lay.bm_words, 1)));
+  RoutesSweep p{};
+  p.V = V;
+  p.G = G;
+  p.M = gr.m;
+  p.n_src = n_src;
+  p.nb = nb;
+  p.onb = nhb;
+  p.units = units;
+  p.gptr = gr.ptr;
+  p.gnodes = gr.nodes;
+  p.iptr = d.rt_iptr.p;
+  p.inv = d.rt_inv.p;
+  p.nptr = d.rt_nptr.p;
+  p.nnode = d.rt_nnode.p;
+  p.ndist = d.rt_ndist.p;
+  p.nnh = d.rt_nnh.p;
+  p.bdist = reinterpret_cast<const unsigned long long*>(d.base_dist.p);
+  p.bnh = d.base_nh.p;
+  p.bmetric = d.rt_bmetric.p;
+  p.bmnh = d.rt_bnh.p;
+  p.changed = d_changed;
+  p.optr = ptr;
+  p.ogroup = d_group;
+  p.ometric = reinterpret_cast<unsigned long long*>(d_metric);
+  p.onh = d_nh;
+  p.onbest = d_nbest;
+  p.ovl_lds = lay.ovl_lds;
+  p.bm_lds = lay.bm_lds;
+  p.cand_cap = lay.cand_cap;
+  p.g_ovl = d.rt_ovl.p;
+  p.g_bm = d.rt_bm.p;
+  HIP_TRY(launch_whatif_routes(p, lay, false, s));
+  HIP_TRY(launch_delta_scan(d_changed, units, d.rt_tsum.p, ptr, s));
+  unsigned long long tot = 0;
+  HIP_TRY(hipMemcpyAsync(&tot, ptr + units, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *total = tot;
+  if (tot > cap)
+    return fail(OPENR_SPF_E2BIG, "%llu routes changed, cap %llu (ptr and changed_routes are filled, entries are not)",
+                tot, (unsigned long long)cap);
+  if (tot) {
+    HIP_TRY(launch_whatif_routes(p, lay, true, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  return OPENR_SPF_OK;
+}
+
+// openr_spf_routes: sources split in contiguous blocks across the devices
+int routes_host(openr_spf_ctx* ctx, const uint32_t* sources, uint32_t n, uint32_t flags, const openr_spf_groups_t* g,
+                uint64_t* metric, uint8_t* nh, uint32_t nh_bytes, uint32_t* n_best) {
+  clear_launch_trace();
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  int rc = check_groups_host(ctx, g);
+  if (rc) return rc;
+  if (n && !sources) return fail(OPENR_SPF_EINVAL, "null sources");
+  if (n && g->n_groups && !metric) return fail(OPENR_SPF_EINVAL, "null metric");
+  const uint32_t need = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
+  if (nh && nh_bytes < need) return fail(OPENR_SPF_EINVAL, "nh_bytes %u < required %u", nh_bytes, need);
+  for (uint32_t i = 0; i < n; ++i)
+    if (sources[i] >= ctx->V) return fail(OPENR_SPF_EINVAL, "source %u out of range (V=%u)", sources[i], ctx->V);
+  if ((rc = check_routes_metric(ctx, flags)) != OPENR_SPF_OK) return rc;
+  const uint32_t G = g->n_groups;
+  if (!n || !G) return OPENR_SPF_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint32_t nd = (uint32_t)ctx->devs.size();
+  const uint32_t per = (n + nd - 1) / std::max<uint32_t>(nd, 1);
+  for (uint32_t di = 0; di < nd; ++di) {
+    Device& d = ctx->devs[di];
+    const uint32_t b = std::min(n, di * per), e = std::min(n, b + per), m = e - b;
+    if (!m) continue;
+    const size_t mg = (size_t)m * G;
+    HIP_TRY(hipSetDevice(d.ordinal));
+    DevGroups gr;
+    if ((rc = upload_groups(d, g, &gr)) != OPENR_SPF_OK) return rc;
+    HIP_TRY(d.src.reserve(m));
+    HIP_TRY(d.rt_ometric.reserve(mg));
+    if (nh) HIP_TRY(d.rt_onh.reserve(mg * nh_bytes));
+    if (n_best) HIP_TRY(d.rt_onbest.reserve(mg));
+    HIP_TRY(hipMemcpyAsync(d.src.p, sources + b, m * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    if ((rc = routes_on_device(ctx, d, d.src.p, m, flags, gr, reinterpret_cast<uint64_t*>(d.rt_ometric.p),
+                               nh ? d.rt_onh.p : nullptr, nh_bytes, n_best ? d.rt_onbest.p : nullptr, d.stream)) !=
+        OPENR_SPF_OK)
+      return rc;
+    const size_t o = (size_t)b * G;
+    HIP_TRY(hipMemcpyAsync(metric + o, d.rt_ometric.p, mg * sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+    if (nh) HIP_TRY(hipMemcpyAsync(nh + o * nh_bytes, d.rt_onh.p, mg * nh_bytes, hipMemcpyDeviceToHost, d.stream));
+    if (n_best)
+      HIP_TRY(hipMemcpyAsync(n_best + o, d.rt_onbest.p, mg * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+  }
+  for (uint32_t di = 0; di < nd; ++di) {
+    if (std::min(n, di * per) >= n) continue;
+    HIP_TRY(hipSetDevice(ctx->devs[di].ordinal));
+    HIP_TRY(hipStreamSynchronize(ctx->devs[di].stream));
+  }
+  ctx->stats.last_batch_ms =
+      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return OPENR_SPF_OK;
+}
+
+// openr_spf_whatif_routes: sets split in contiguous blocks across the devices, each device's
+// CSR appended to the caller's at the running total, each unit's entries sorted by group id
+int whatif_routes_host(openr_spf_ctx* ctx, const WhatifUnits& hu, const uint32_t* sources, uint32_t n_sources,
+                       uint32_t flags, const openr_spf_groups_t* g, uint32_t* changed,
+                       openr_spf_whatif_routes_t* delta, uint64_t* out_solved) {
+  clear_launch_trace();
+  const uint32_t n_sets = hu.n;
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  int rc = check_whatif_host(ctx, hu, sources, n_sources, changed);
+  if (rc) return rc;
+  if ((rc = check_groups_host(ctx, g)) != OPENR_SPF_OK) return rc;
+  if (delta && !delta->ptr) return fail(OPENR_SPF_EINVAL, "null delta->ptr");
+  if (delta && delta->cap && (!delta->group || !delta->metric || !delta->nh))
+    return fail(OPENR_SPF_EINVAL, "null delta->group, metric or nh");
+  if ((rc = check_routes_metric(ctx, flags)) != OPENR_SPF_OK) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint32_t need = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
+  const uint32_t nhb = delta ? delta->nh_bytes : need;
+  const uint64_t cap = delta ? delta->cap : 0u;
+  const bool want_nbest = delta && delta->n_best;
+  std::vector<uint32_t> rebased, idx;
+  std::vector<uint64_t> ptr;
+  const uint32_t nd = (uint32_t)ctx->devs.size();
+  const uint32_t per = (n_sets + nd - 1) / std::max<uint32_t>(nd, 1);
+  uint64_t solved_total = 0, at = 0;
+  bool over = false;
+  if (delta) delta->ptr[0] = 0;
+  if (out_solved) *out_solved = 0;
+  for (uint32_t di = 0; di < nd; ++di) {
+    Device& d = ctx->devs[di];
+    const uint32_t b = std::min(n_sets, di * per), e = std::min(n_sets, b + per), m = e - b;
+    if (!m || !n_sources) continue;
+    const size_t mu = (size_t)m * n_sources;
+    HIP_TRY(hipSetDevice(d.ordinal));
+    WhatifUnits un;
+    if ((rc = upload_whatif_units(d, hu, b, m, &rebased, &un)) != OPENR_SPF_OK) return rc;
+    DevGroups gr;
+    if ((rc = upload_groups(d, g, &gr)) != OPENR_SPF_OK) return rc;
+    HIP_TRY(d.win_src.reserve(n_sources));
+    HIP_TRY(d.rt_ochanged.reserve(mu));
+    HIP_TRY(d.rt_optr.reserve(mu + 1));
+    HIP_TRY(hipMemcpyAsync(d.win_src.p, sources, n_sources * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    // the device's entries land in library buffers sized to the room left in the caller's
+    const uint64_t room = cap > at ? cap - at : 0;
+    HIP_TRY(d.rt_ogroup.reserve(std::max<uint64_t>(room, 1)));
+    HIP_TRY(d.rt_ometric.reserve(std::max<uint64_t>(room, 1)));
+    HIP_TRY(d.rt_onh.reserve(std::max<uint64_t>(room * nhb, 1)));
+    if (want_nbest) HIP_TRY(d.rt_onbest.reserve(std::max<uint64_t>(room, 1)));
+    uint64_t total = 0, solved = 0;
+    rc = whatif_routes_on_device(ctx, d, un, d.win_src.p, n_sources, flags, gr, d.rt_ochanged.p,
+                                 reinterpret_cast<uint64_t*>(d.rt_optr.p), d.rt_ogroup.p,
+                                 reinterpret_cast<uint64_t*>(d.rt_ometric.p), d.rt_onh.p,
+                                 want_nbest ? d.rt_onbest.p : nullptr, room, nhb, d.stream, &total, &solved);
+    if (rc && rc != OPENR_SPF_E2BIG) return rc;
+    over |= rc == OPENR_SPF_E2BIG;
+    solved_total += solved;
+    ptr.resize(mu + 1);
+    HIP_TRY(hipMemcpyAsync(changed + (size_t)b * n_sources, d.rt_ochanged.p, mu * sizeof(uint32_t),
+                           hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipMemcpyAsync(ptr.data(), d.rt_optr.p, (mu + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+    const bool fits = delta && !over && total <= room;
+    if (fits && total) {
+      HIP_TRY(hipMemcpyAsync(delta->group + at, d.rt_ogroup.p, total * 4u, hipMemcpyDeviceToHost, d.stream));
+      HIP_TRY(hipMemcpyAsync(delta->metric + at, d.rt_ometric.p, total * 8u, hipMemcpyDeviceToHost, d.stream));
+      HIP_TRY(hipMemcpyAsync(delta->nh + at * nhb, d.rt_onh.p, total * nhb, hipMemcpyDeviceToHost, d.stream));
+      if (want_nbest)
+        HIP_TRY(hipMemcpyAsync(delta->n_best + at, d.rt_onbest.p, total * 4u, hipMemcpyDeviceToHost, d.stream));
+    }
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    for (size_t u = 0; delta && u < mu; ++u) {
+      const size_t gu = (size_t)b * n_sources + u;
+      delta->ptr[gu + 1] = at + ptr[u + 1];
+      const uint32_t c = (uint32_t)(ptr[u + 1] - ptr[u]);
+      if (!fits || c < 2) continue;
+      // each unit's groups ascending (the device keeps the kernel's order)
+      const uint64_t o = at + ptr[u];
+      idx.resize(c);
+      for (uint32_t k = 0; k < c; ++k) idx[k] = k;
+      std::sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return delta->group[o + x] < delta->group[o + y]; });
+      std::vector<uint32_t> tg(c), tb(c);
+      std::vector<uint64_t> tm(c);
+      std::vector<uint8_t> th((size_t)c * nhb);
+      for (uint32_t k = 0; k < c; ++k) {
+        tg[k] = delta->group[o + idx[k]];
+        tm[k] = delta->metric[o + idx[k]];
+        if (want_nbest) tb[k] = delta->n_best[o + idx[k]];
+        std::memcpy(&th[(size_t)k * nhb], delta->nh + (o + idx[k]) * nhb, nhb);
+      }
+      std::memcpy(delta->group + o, tg.data(), c * 4u);
+      std::memcpy(delta->metric + o, tm.data(), c * 8u);
+      if (want_nbest) std::memcpy(delta->n_best + o, tb.data(), c * 4u);
+      std::memcpy(delta->nh + o * nhb, th.data(), (size_t)c * nhb);
+    }
+    at += total;
+  }
+  ctx->stats.last_batch_ms =
+      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (out_solved) *out_solved = solved_total;
+  if (delta && (over || at > cap))
+    return fail(OPENR_SPF_E2BIG, "%llu routes changed, cap %llu (ptr and changed_routes are filled, entries are not)",
+                (unsigned long long)at, (unsigned long long)cap);
+  return OPENR_SPF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1529,6 +1906,12 @@ void openr_spf_destroy(openr_spf_ctx* ctx) {
     d.wbeg.release();
     d.wend.release();
     d.win_ptr.release();
+    void* routes[] = {d.rt_nptr.p,  d.rt_ndist.p, d.rt_bmetric.p,  d.rt_iptr.p,   d.rt_tsum.p,   d.rt_optr.p,
+                      d.rt_ometric.p, d.rt_nchanged.p, d.rt_nnode.p, d.rt_inv.p,    d.rt_icnt.p,   d.rt_icur.p,
+                      d.rt_large.p, d.rt_ovl.p,   d.rt_bm.p,       d.rt_gptr.p,   d.rt_gnodes.p, d.rt_ochanged.p,
+                      d.rt_ogroup.p, d.rt_onbest.p, d.rt_nnh.p,     d.rt_bnh.p,    d.rt_onh.p};
+    for (void* p : routes)
+      if (p) (void)hipFree(p);
     void* sweep[] = {d.base_dist.p, d.base_tight.p, d.wdist.p, d.base_nh.p, d.wnh.p, d.wsrc.p, d.wlink.p,
                      d.wunit.p,     d.wcount.p,     d.wiota.p, d.base_tin.p, d.win_links.p, d.win_src.p, d.wchanged.p, d.wchanged_t.p,
                      d.kbase.p,     d.krows.p,      d.krows16.p, d.kign.p,  d.kend.p, d.ksrc.p,      d.kptr.p,    d.kstatus.p,
@@ -2302,6 +2685,84 @@ int openr_spf_whatif_sets_delta(openr_spf_ctx* ctx, const uint32_t* set_ptr, con
   if (n_sets && !set_ptr) return fail(OPENR_SPF_EINVAL, "null set_ptr");
   return whatif_delta_host(ctx, host_sets(set_ptr, set_links, n_sets), sources, n_sources, flags, changed, delta,
                            out_solved);
+}
+
+int openr_spf_routes(openr_spf_ctx* ctx, const uint32_t* sources, uint32_t n, uint32_t flags,
+                     const openr_spf_groups_t* groups, uint64_t* metric, uint8_t* nh, uint32_t nh_bytes,
+                     uint32_t* n_best) {
+  return routes_host(ctx, sources, n, flags, groups, metric, nh, nh_bytes, n_best);
+}
+
+int openr_spf_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_sources, uint32_t n,
+                            uint32_t flags, const uint32_t* d_group_ptr, const uint32_t* d_group_nodes,
+                            uint32_t n_groups, uint32_t n_group_nodes, uint64_t* d_metric, uint8_t* d_nh,
+                            uint32_t nh_bytes, uint32_t* d_n_best, void* stream) {
+  clear_launch_trace();
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (device_index < 0 || device_index >= (int)ctx->devs.size())
+    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+  if ((n && !d_sources) || (n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes) ||
+      (n && n_groups && !d_metric))
+    return fail(OPENR_SPF_EINVAL, "null sources, groups or metric");
+  const uint32_t need = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
+  if (d_nh && nh_bytes < need) return fail(OPENR_SPF_EINVAL, "nh_bytes %u < required %u", nh_bytes, need);
+  int rc = check_routes_metric(ctx, flags);
+  if (rc) return rc;
+  Device& d = ctx->devs[device_index];
+  HIP_TRY(hipSetDevice(d.ordinal));
+  DevGroups gr;
+  gr.ptr = d_group_ptr;
+  gr.nodes = d_group_nodes;
+  gr.n = n_groups;
+  gr.m = n_group_nodes;
+  return routes_on_device(ctx, d, d_sources, n, flags, gr, d_metric, d_nh, nh_bytes, d_n_best,
+                          stream ? reinterpret_cast<hipStream_t>(stream) : d.stream);
+}
+
+int openr_spf_whatif_routes(openr_spf_ctx* ctx, const uint32_t* set_ptr, const uint32_t* set_links, uint32_t n_sets,
+                            const uint32_t* sources, uint32_t n_sources, uint32_t flags,
+                            const openr_spf_groups_t* groups, uint32_t* changed_routes,
+                            openr_spf_whatif_routes_t* delta, uint64_t* out_solved) {
+  if (n_sets && !set_ptr) return fail(OPENR_SPF_EINVAL, "null set_ptr");
+  return whatif_routes_host(ctx, host_sets(set_ptr, set_links, n_sets), sources, n_sources, flags, groups,
+                            changed_routes, delta, out_solved);
+}
+
+int openr_spf_whatif_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_set_ptr,
+                                   const uint32_t* d_set_links, uint32_t n_sets, uint32_t n_set_links,
+                                   const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                                   const uint32_t* d_group_ptr, const uint32_t* d_group_nodes, uint32_t n_groups,
+                                   uint32_t n_group_nodes, uint32_t* d_changed_routes, uint64_t* d_ptr,
+                                   uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh, uint32_t* d_n_best,
+                                   uint64_t cap, uint32_t nh_bytes, void* stream, uint64_t* out_total,
+                                   uint64_t* out_solved) {
+  clear_launch_trace();
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (device_index < 0 || device_index >= (int)ctx->devs.size())
+    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+  if ((n_sets && !d_set_ptr) || (n_sources && !d_sources) || (n_sets && n_sources && !d_changed_routes) || !d_ptr)
+    return fail(OPENR_SPF_EINVAL, "null sets, sources, changed_routes or ptr");
+  if ((n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes))
+    return fail(OPENR_SPF_EINVAL, "null group_ptr or group_nodes");
+  if (cap && (!d_group || !d_metric || !d_nh)) return fail(OPENR_SPF_EINVAL, "null route buffer");
+  int rc = check_routes_metric(ctx, flags);
+  if (rc) return rc;
+  Device& d = ctx->devs[device_index];
+  HIP_TRY(hipSetDevice(d.ordinal));
+  DevGroups gr;
+  gr.ptr = d_group_ptr;
+  gr.nodes = d_group_nodes;
+  gr.n = n_groups;
+  gr.m = n_group_nodes;
+  uint64_t total = 0, solved = 0;
+  rc = whatif_routes_on_device(ctx, d, device_sets(d_set_ptr, d_set_links, n_sets, n_set_links), d_sources, n_sources,
+                               flags, gr, d_changed_routes, d_ptr, d_group, d_metric, d_nh, d_n_best, cap, nh_bytes,
+                               stream ? reinterpret_cast<hipStream_t>(stream) : d.stream, &total, &solved);
+  if (out_total) *out_total = total;
+  if (out_solved) *out_solved = solved;
+  return rc;
 }
 
 int openr_spf_ksp2(openr_spf_ctx* ctx, const uint32_t* src, const uint32_t* dst, uint32_t n_pairs,

@@ -294,6 +294,65 @@ hipError_t launch_whatif_group(const DevGraph& g, const uint32_t* links, uint32_
 // 0 when the grouped repair cannot run on the graph (ids, next-hop width, degree, LDS)
 uint32_t whatif_group_lds_bytes(uint32_t V, uint32_t E, uint32_t nb, bool dist64, uint32_t max_deg);
 
+// Route-level results (spf_routes.hip). A group table is a CSR over G prefix groups: group
+// k = gnodes[gptr[k], gptr[k + 1]) (M entries, node ids ascending inside a group); its
+// route in an SPF row is metric = min dist over the members, nh = OR of the next-hop bytes
+// of the members at that minimum, n_best = their number (Decision.cpp:1094-1167).
+// routes_reduce: metric [n][G], onh [n][G][onb] (nullable; zero past nb) and nbest [n][G]
+// (nullable) from row-major dist [n][V] / nh [n][V][nb]. A lane owns a small group, a wave
+// a large one; scratch holds routes_reduce_scratch_words(G) u32.
+uint32_t routes_reduce_scratch_words(uint32_t G);
+hipError_t launch_routes_reduce(uint32_t n, uint32_t V, uint32_t G, uint32_t M, const uint32_t* gptr,
+                                const uint32_t* gnodes, const uint64_t* dist, const uint8_t* nh, uint32_t nb,
+                                uint64_t* metric, uint8_t* onh, uint32_t onb, uint32_t* nbest, uint32_t* scratch,
+                                int num_cus, hipStream_t s);
+// Inverse map node -> groups: iptr [V + 1] (u64, scanned through tsum: one u64 per 4096
+// nodes) and inv [M] group ids; cnt / cur are [V] scratch.
+hipError_t launch_routes_inverse(uint32_t V, uint32_t G, uint32_t M, const uint32_t* gptr, const uint32_t* gnodes,
+                                 uint32_t* cnt, uint32_t* cur, unsigned long long* tsum, unsigned long long* iptr,
+                                 uint32_t* inv, int num_cus, hipStream_t s);
+// Route-level what-if pass over the units of a link-set sweep (unit u = i * n_src + j): the
+// unit's node delta (CSR nptr / nnode / ndist / nnh, nb bytes per next-hop entry) overlaid
+// on base row j, the groups with a changed member recomputed and compared with base route
+// (j, k). The count pass writes changed[u] for the units with a non-empty node delta (the
+// caller zeroes changed[] first); the emit pass writes every changed route at optr[u] + its
+// rank in the pass (any order inside a unit).
+struct RoutesSweep {
+  uint32_t V, G, M, n_src, nb, onb;
+  size_t units;
+  const uint32_t* gptr;
+  const uint32_t* gnodes;
+  const unsigned long long* iptr;
+  const uint32_t* inv;
+  const unsigned long long* nptr;
+  const uint32_t* nnode;
+  const unsigned long long* ndist;
+  const uint8_t* nnh;
+  const unsigned long long* bdist;    // base rows [n_src][V]
+  const uint8_t* bnh;                 // [n_src][V][nb]
+  const unsigned long long* bmetric;  // base routes [n_src][G]
+  const uint8_t* bmnh;                // [n_src][G][nb]
+  uint32_t* changed;                  // [units]
+  const unsigned long long* optr;     // emit pass: [units + 1]
+  uint32_t* ogroup;
+  unsigned long long* ometric;
+  uint8_t* onh;                       // [.][onb], zero past nb
+  uint32_t* onbest;                   // nullable
+  uint32_t ovl_lds, bm_lds, cand_cap; // RoutesSweepLayout
+  uint32_t* g_ovl;                    // [grid][V] when the overlay is not in LDS
+  uint32_t* g_bm;                     // [grid][ceil(G / 32)] when the bitmap is not
+};
+// Where the per-workgroup structures live for a (V, G) and the grid that follows: the
+// node -> entry overlay and the candidate bitmap in LDS when they fit their limits, else
+// in global scratch of ovl_words / bm_words u32; a candidate list of cand_cap groups whose
+// overflow falls back to a scan of the bitmap. No limit changes a result.
+struct RoutesSweepLayout {
+  uint32_t ovl_lds = 1, bm_lds = 1, cand_cap = 0, lds_bytes = 0, grid = 1;
+  size_t ovl_words = 0, bm_words = 0;
+};
+RoutesSweepLayout whatif_routes_layout(uint32_t V, uint32_t G, size_t units, int num_cus);
+hipError_t launch_whatif_routes(const RoutesSweep& p, const RoutesSweepLayout& l, bool emit, hipStream_t s);
+
 // Incremental mirror updates (spf_update.hip).
 // In-place attribute patch of the device mirror: each record overwrites one element of
 // one DevGraph array (structure — rows, columns, link ids — never changes).

@@ -50,6 +50,10 @@ EXPORTS = (
     "openr_spf_whatif_sets_device",
     "openr_spf_whatif_sets_delta",
     "openr_spf_whatif_sets_delta_device",
+    "openr_spf_routes",
+    "openr_spf_routes_device",
+    "openr_spf_whatif_routes",
+    "openr_spf_whatif_routes_device",
     "openr_spf_ksp2",
     "openr_spf_ksp2_device",
     "openr_spf_host_alloc",
@@ -103,6 +107,26 @@ class WhatifDelta(ctypes.Structure):  # openr_spf_whatif_delta_t
         ("node", ctypes.c_void_p),
         ("dist", ctypes.c_void_p),
         ("nh", ctypes.c_void_p),
+        ("cap", ctypes.c_uint64),
+        ("nh_bytes", ctypes.c_uint32),
+    ]
+
+
+class SpfGroups(ctypes.Structure):  # openr_spf_groups_t
+    _fields_ = [
+        ("n_groups", ctypes.c_uint32),
+        ("group_ptr", ctypes.c_void_p),
+        ("group_nodes", ctypes.c_void_p),
+    ]
+
+
+class WhatifRoutes(ctypes.Structure):  # openr_spf_whatif_routes_t
+    _fields_ = [
+        ("ptr", ctypes.c_void_p),
+        ("group", ctypes.c_void_p),
+        ("metric", ctypes.c_void_p),
+        ("nh", ctypes.c_void_p),
+        ("n_best", ctypes.c_void_p),
         ("cap", ctypes.c_uint64),
         ("nh_bytes", ctypes.c_uint32),
     ]
@@ -164,6 +188,13 @@ def load_library():
     l.openr_spf_whatif_sets_delta_device.argtypes = [vp, ctypes.c_int, vp, vp, u32, u32, vp, u32, u32, vp, vp, vp, vp,
                                                      vp, ctypes.c_uint64, u32, vp, P(ctypes.c_uint64),
                                                      P(ctypes.c_uint64)]
+    l.openr_spf_routes.argtypes = [vp, vp, u32, u32, P(SpfGroups), vp, vp, u32, vp]
+    l.openr_spf_routes_device.argtypes = [vp, ctypes.c_int, vp, u32, u32, vp, vp, u32, u32, vp, vp, u32, vp, vp]
+    l.openr_spf_whatif_routes.argtypes = [vp, vp, vp, u32, vp, u32, u32, P(SpfGroups), vp, P(WhatifRoutes),
+                                          P(ctypes.c_uint64)]
+    l.openr_spf_whatif_routes_device.argtypes = [vp, ctypes.c_int, vp, vp, u32, u32, vp, u32, u32, vp, vp, u32, u32,
+                                                 vp, vp, vp, vp, vp, vp, ctypes.c_uint64, u32, vp,
+                                                 P(ctypes.c_uint64), P(ctypes.c_uint64)]
     l.openr_spf_ksp2.argtypes = [vp, vp, vp, u32, u32, vp, vp]
     l.openr_spf_ksp2_device.argtypes = [vp, ctypes.c_int, vp, u32, vp, vp, u32, u32, vp, vp, vp]
     l.openr_spf_host_alloc.argtypes = [ctypes.c_size_t, P(vp)]
@@ -439,6 +470,89 @@ class SpfEngine:
             self._ctx, device_index, vp(d_set_ptr or None), vp(d_set_links or None), n_sets, n_set_links,
             vp(d_sources), n_sources, flags, vp(d_changed), vp(d_ptr), vp(d_node or None), vp(d_dist or None),
             vp(d_nh or None), cap, nh_bytes, vp(stream or None), ctypes.byref(total), ctypes.byref(solved))
+        if not (allow_overflow and rc == E2BIG):
+            _check(rc)
+        return int(total.value), int(solved.value)
+
+    def routes(self, sources: Sequence[int], groups: Sequence[Sequence[int]], use_link_metric: bool = True,
+               want_nh: bool = True, want_n_best: bool = True, nh_bytes: Optional[int] = None):
+        """Best-path selection over prefix groups (openr_spf_routes): (metric[n, G] u64,
+        nh[n, G, nh_bytes] u8 | None, n_best[n, G] u32 | None). Group k's route at a source is
+        the minimum distance over its members and the OR of their next-hop sets at that
+        minimum. ``groups``: node-id lists, strictly ascending (topology.prefix_groups)."""
+        gp, gn = _ignore_arrays(groups, len(groups))
+        src = np.ascontiguousarray(sources, dtype=np.uint32)
+        n, G = int(src.shape[0]), len(groups)
+        nb = self.nh_bytes if nh_bytes is None else nh_bytes
+        metric = np.zeros((n, G), dtype=np.uint64)
+        nh = np.zeros((n, G, nb), dtype=np.uint8) if want_nh else None
+        n_best = np.zeros((n, G), dtype=np.uint32) if want_n_best else None
+        gs = SpfGroups(G, _p(gp), _p(gn))
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        _check(self._lib.openr_spf_routes(self._ctx, _p(src), n, flags, ctypes.byref(gs), _p(metric), _p(nh), nb,
+                                          _p(n_best)))
+        return metric, nh, n_best
+
+    def routes_device(self, d_sources: int, n: int, d_group_ptr: int, d_group_nodes: int, n_groups: int,
+                      n_group_nodes: int, d_metric: int, d_nh: int = 0, nh_bytes: int = 0, d_n_best: int = 0,
+                      use_link_metric: bool = True, stream: int = 0, device_index: int = 0) -> None:
+        """Device-pointer form (openr_spf_routes_device): enqueues on ``stream``."""
+        vp = ctypes.c_void_p
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        _check(self._lib.openr_spf_routes_device(self._ctx, device_index, vp(d_sources), n, flags,
+                                                 vp(d_group_ptr or None), vp(d_group_nodes or None), n_groups,
+                                                 n_group_nodes, vp(d_metric), vp(d_nh or None),
+                                                 nh_bytes or self.nh_bytes, vp(d_n_best or None), vp(stream or None)))
+
+    def whatif_routes(self, sets: Sequence[Sequence[int]], sources: Sequence[int], groups: Sequence[Sequence[int]],
+                      use_link_metric: bool = True, cap: Optional[int] = None, nh_bytes: Optional[int] = None):
+        """Route-level link-set failure sweep (openr_spf_whatif_routes): (changed_routes[n_sets,
+        n_sources] u32, ptr[n_units + 1] u64, group u32, metric u64, nh[entries, nh_bytes] u8,
+        n_best u32, SPFs run). Unit u = i * n_sources + j owns entries [ptr[u], ptr[u + 1]):
+        the groups whose route (metric or next hops) the failure of sets[i] changes at
+        sources[j], group ids ascending, with the new route. cap None: sized from a
+        count-only pass."""
+        n = len(sets)
+        sp, sl = _ignore_arrays(sets, n)
+        gp, gn = _ignore_arrays(groups, len(groups))
+        gs = SpfGroups(len(groups), _p(gp), _p(gn))
+        src = np.ascontiguousarray(sources, dtype=np.uint32)
+        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
+        solved = ctypes.c_uint64()
+        if cap is None:
+            _check(self._lib.openr_spf_whatif_routes(self._ctx, _p(sp), _p(sl), n, _p(src), src.shape[0], flags,
+                                                     ctypes.byref(gs), _p(changed), None, ctypes.byref(solved)))
+            cap = int(changed.sum(dtype=np.uint64))
+        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
+        group = np.zeros(max(cap, 1), dtype=np.uint32)
+        metric = np.zeros(max(cap, 1), dtype=np.uint64)
+        nh = np.zeros((max(cap, 1), nb), dtype=np.uint8)
+        n_best = np.zeros(max(cap, 1), dtype=np.uint32)
+        d = WhatifRoutes(_p(ptr), _p(group), _p(metric), _p(nh), _p(n_best), cap, nb)
+        _check(self._lib.openr_spf_whatif_routes(self._ctx, _p(sp), _p(sl), n, _p(src), src.shape[0], flags,
+                                                 ctypes.byref(gs), _p(changed), ctypes.byref(d),
+                                                 ctypes.byref(solved)))
+        k = int(ptr[-1])
+        return changed, ptr, group[:k], metric[:k], nh[:k], n_best[:k], int(solved.value)
+
+    def whatif_routes_device(self, d_set_ptr: int, d_set_links: int, n_sets: int, n_set_links: int, d_sources: int,
+                             n_sources: int, d_group_ptr: int, d_group_nodes: int, n_groups: int,
+                             n_group_nodes: int, d_changed: int, d_ptr: int, d_group: int, d_metric: int, d_nh: int,
+                             d_n_best: int, cap: int, nh_bytes: int, use_link_metric: bool = True, stream: int = 0,
+                             device_index: int = 0, allow_overflow: bool = False) -> Tuple[int, int]:
+        """Device-pointer form: (total entries, SPFs run). d_ptr [n_units + 1] u64 CSR; unit
+        u's entries are [ptr[u], ptr[u + 1]) in the kernel's order."""
+        vp = ctypes.c_void_p
+        total = ctypes.c_uint64()
+        solved = ctypes.c_uint64()
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        rc = self._lib.openr_spf_whatif_routes_device(
+            self._ctx, device_index, vp(d_set_ptr or None), vp(d_set_links or None), n_sets, n_set_links,
+            vp(d_sources), n_sources, flags, vp(d_group_ptr or None), vp(d_group_nodes or None), n_groups,
+            n_group_nodes, vp(d_changed), vp(d_ptr), vp(d_group or None), vp(d_metric or None), vp(d_nh or None),
+            vp(d_n_best or None), cap, nh_bytes, vp(stream or None), ctypes.byref(total), ctypes.byref(solved))
         if not (allow_overflow and rc == E2BIG):
             _check(rc)
         return int(total.value), int(solved.value)

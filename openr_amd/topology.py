@@ -488,3 +488,22 @@ def srlg_sets(g: CsrGraph, groups: Iterable[Iterable[int]]) -> List[List[int]]:
             raise ValueError(f"group {k}: link {bad} out of range (L={g.num_links})")
         out.append(links)
     return out
+
+
+def prefix_groups(g: CsrGraph, groups: Iterable[Iterable[int]]) -> List[List[int]]:
+    """Caller-given prefix groups (the advertisers of each prefix) as a group table for
+    ``SpfEngine.routes`` / ``whatif_routes``: every group validated (node ids in
+    [0, num_nodes)), de-duplicated and sorted. Empty groups are kept."""
+    out = []
+    for k, grp in enumerate(groups):
+        nodes = sorted(set(int(v) for v in grp))
+        if nodes and not (0 <= nodes[0] and nodes[-1] < g.num_nodes):
+            bad = nodes[0] if nodes[0] < 0 else nodes[-1]
+            raise ValueError(f"group {k}: node {bad} out of range (V={g.num_nodes})")
+        out.append(nodes)
+    return out
+
+
+def loopback_groups(g: CsrGraph) -> List[List[int]]:
+    """One singleton group per node: every router's loopback prefix."""
+    return [[v] for v in range(g.num_nodes)]
