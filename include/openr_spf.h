@@ -27,6 +27,9 @@
  *   openr_spf_routes           SpfSolver::getMinCostNodes + the shortest-path half of
  *                              getNextHopsWithMetric (Decision.cpp:1094-1167) over prefix
  *                              groups, for a batch of sources
+ *   openr_spf_lfa_routes       the other half of getNextHopsWithMetric: loop-free alternates
+ *                              (RFC 5286, Decision.cpp:1169-1204) of every (source, prefix
+ *                              group), from the rows of the sources and their neighbours
  *   openr_spf_whatif_routes    the link-set sweep resolved to routes: per (failure set,
  *                              source) the groups whose route changed, with the new route
  *   openr_spf_ksp2             LinkState::getKthPaths(src, dst, 1 and 2) (LinkState.cpp:762-791)
@@ -345,7 +348,8 @@ typedef struct {
    group_ptr that does not ascend or a group that is not strictly ascending is
    OPENR_SPF_EINVAL. The sources are solved into library scratch (in chunks when n x V rows
    exceed the what-if chunk budget) and reduced on the device; they are split in contiguous
-   blocks across the context's devices. */
+   blocks across the context's devices. The LFA half of getNextHopsWithMetric
+   (Decision.cpp:1169-1204) is openr_spf_lfa_routes, which returns these routes too. */
 int openr_spf_routes(openr_spf_ctx* ctx, const uint32_t* sources, uint32_t n, uint32_t flags,
                      const openr_spf_groups_t* groups, uint64_t* metric, uint8_t* nh, uint32_t nh_bytes,
                      uint32_t* n_best);
@@ -357,6 +361,70 @@ int openr_spf_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t
                             uint32_t flags, const uint32_t* d_group_ptr, const uint32_t* d_group_nodes,
                             uint32_t n_groups, uint32_t n_group_nodes, uint64_t* d_metric, uint8_t* d_nh,
                             uint32_t nh_bytes, uint32_t* d_n_best, void* stream);
+
+/* Loop-free alternates (LFA, RFC 5286) over prefix groups for a batch of sources: the LFA
+   half of SpfSolver::getNextHopsWithMetric (Decision.cpp:1169-1204), i.e.
+   getNextHopsWithMetric(me, group, perDestination = false, one area) with computeLfaPaths_
+   on, applied literally to the rows openr_spf_solve gives under `flags`. For source i
+   (node s) and group k:
+     metric, nh    exactly what openr_spf_routes returns: the minimum over the members in the
+                   SpfResult and the OR of the members' sets at that minimum
+     alt[i][k][b]  empty when metric is UINT64_MAX (no member reached, an empty group): the
+                   reference continues before its LFA loop (:1156-1158), and metric + toMe is
+                   never formed there (it would wrap). Otherwise every distinct neighbour n of
+                   s with at least one up link s-n is tested; b is n's next-hop bit
+                   (openr_spf_neighbor_map) and toMe = dist_n(s). Every member d of the group
+                   is tested, not only those at the minimum: d qualifies when dist_n(d) !=
+                   UINT64_MAX and dist_n(d) < metric + toMe. Bit b is set iff some member
+                   qualifies. Same layout as nh: nh_bytes bytes, zero past the graph's width.
+     n_alt[i][k]   popcount(alt) (nullable)
+     alt_metric    per set bit b, the value the reference keeps under key (n, ""): the
+                   minimum of dist_n(d) over the qualifying members, and of metric - dist_s(n)
+                   too when b is in nh (:1163-1166, :1196-1200)
+   The RIB's next-hop set is nh | alt; the LFA-only next hops are alt & ~nh. A neighbour
+   reached only over down links is never tested. An overloaded neighbour is tested (its own
+   SPF expands it as the source). A group that contains s has metric 0 and an empty nh, and
+   its other members can still qualify a neighbour. The hop-count form applies the same rule
+   to hop rows. perDestination = true (the KSP2 / BGP form), multi-area ECMP and LFA over
+   what-if rows are not covered.
+   entries (nullable: no entry output, one pass) is a CSR over units u = i * n_groups + k:
+   unit u's alternates are [ptr[u], ptr[u + 1]), next-hop bits ascending. OPENR_SPF_E2BIG
+   means sum(n_alt) > cap and nothing else: ptr, n_alt, metric, nh and alt are filled, the
+   entries are not. cap = 0 gives counts and ptr only. metric must be non-NULL; nh, alt and
+   n_alt may be NULL; nh_bytes >= openr_spf_nh_bytes. Group validation and errors (EINVAL,
+   ENOTSUP on a usable metric outside [1, 2^31-1] under link metric) are those of
+   openr_spf_routes. The rows needed are the distinct nodes among the sources and their up
+   neighbours; each is solved once into library scratch (next hops for the sources only).
+   When they exceed the what-if chunk budget the sources are processed in chunks, each with
+   its own neighbour closure: a row two chunks need is solved in both, and so is a source
+   listed twice. *out_solved (nullable) = rows solved, also added to stats.spf_runs. Sources
+   are split in contiguous blocks across the context's devices. */
+typedef struct {
+  uint64_t* ptr;      /* [n * n_groups + 1], unit u = i * n_groups + k */
+  uint32_t* nbr;      /* [cap] next-hop bit index, ascending inside a unit */
+  uint64_t* metric;   /* [cap] alt_metric */
+  uint64_t cap;       /* entries the caller allocated */
+} openr_spf_lfa_entries_t;
+int openr_spf_lfa_routes(openr_spf_ctx* ctx, const uint32_t* sources, uint32_t n, uint32_t flags,
+                         const openr_spf_groups_t* groups, uint64_t* metric, uint8_t* nh, uint8_t* alt,
+                         uint32_t nh_bytes, uint32_t* n_alt, openr_spf_lfa_entries_t* entries,
+                         uint64_t* out_solved);
+
+/* Device-buffer form (every buffer device memory; groups as in openr_spf_routes_device: not
+   validated, a slice is clamped to n_group_nodes and a member >= V counts as unreached).
+   d_nh, d_alt and d_n_alt may be NULL. d_ptr NULL: no entry output (d_nbr, d_alt_metric and
+   cap are ignored). Else d_ptr [n * n_groups + 1] is always filled and *out_total (host,
+   nullable) = sum(n_alt); when it exceeds cap the entries are not written and the call
+   returns OPENR_SPF_E2BIG (cap 0: counts and ptr only). Synchronizes `stream` once per chunk
+   of sources for the number of needed rows (it sizes the solve of the neighbours' rows), and
+   once more per chunk for the total when entries are requested; everything else is
+   enqueued. */
+int openr_spf_lfa_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_sources, uint32_t n,
+                                uint32_t flags, const uint32_t* d_group_ptr, const uint32_t* d_group_nodes,
+                                uint32_t n_groups, uint32_t n_group_nodes, uint64_t* d_metric, uint8_t* d_nh,
+                                uint8_t* d_alt, uint32_t nh_bytes, uint32_t* d_n_alt, uint64_t* d_ptr,
+                                uint32_t* d_nbr, uint64_t* d_alt_metric, uint64_t cap, void* stream,
+                                uint64_t* out_total, uint64_t* out_solved);
 
 /* Route-level what-if sweep: which routes move when a router or a shared-risk group fails,
    i.e. what Decision's route rebuild (getMinCostNodes / getNextHopsWithMetric,

@@ -118,6 +118,12 @@ struct Device {
   DevBuf<uint32_t> rt_nchanged, rt_nnode, rt_inv, rt_icnt, rt_icur, rt_large, rt_ovl, rt_bm;
   DevBuf<uint32_t> rt_gptr, rt_gnodes, rt_ochanged, rt_ogroup, rt_onbest;
   DevBuf<uint8_t> rt_nnh, rt_bnh, rt_onh;
+  // loop-free alternates (spf_lfa.hip): the needed-row bitmaps, their scan and list, the
+  // node -> row index, the neighbour table, and the host form's outputs before they are
+  // copied out (metric / nh share rt_ometric / rt_onh with the routes calls)
+  DevBuf<uint32_t> lf_need, lf_srcbm, lf_cnt, lf_list, lf_rowidx, lf_trow, lf_nalt, lf_onbr;
+  DevBuf<unsigned long long> lf_wptr, lf_tsum, lf_ttome, lf_tfrom, lf_optr, lf_oam;
+  DevBuf<uint8_t> lf_nh, lf_alt;
   // incremental updates: patch records, the last patch's delta edges, refresh work list,
   // host-form refresh rows
   DevBuf<PatchRec> precs;
@@ -1794,6 +1800,271 @@ int whatif_routes_host(openr_spf_ctx* ctx, const WhatifUnits& hu, const uint32_t
   return OPENR_SPF_OK;
 }
 
+// ---- loop-free alternates (spf_lfa.hip) -----------------------------------------------------
+
+// Outputs of openr_spf_lfa_routes[_device] in device memory. nh / alt hold nhb bytes per
+// route; nh, alt and n_alt may be null; the entry arrays are written when `entries` is set
+// (ptr [n * G + 1] then non-null; nbr / alt_metric hold cap entries).
+struct LfaOut {
+  uint64_t* metric = nullptr;
+  uint8_t* nh = nullptr;
+  uint8_t* alt = nullptr;
+  uint32_t nhb = 0;
+  uint32_t* n_alt = nullptr;
+  bool entries = false;
+  uint64_t* ptr = nullptr;
+  uint32_t* nbr = nullptr;
+  uint64_t* alt_metric = nullptr;
+  uint64_t cap = 0;
+};
+
+// openr_spf_lfa_routes[_device] on one device, a chunk of sources at a time. Per chunk: the
+// needed rows (launch_lfa_rows; one synchronization for their count, which sizes the second
+// solve), the sources solved with next hops and the other needed nodes with distances only
+// through the ordinary launcher into library scratch, routes_reduce over the sources' rows,
+// the neighbour table and the count pass; with entries the scan of the counts into ptr
+// (moved behind the chunks before it), one more synchronization for the total, the cap check
+// and the emit pass. All sources are one chunk when V distance rows and their next-hop rows
+// fit the what-if chunk budget; else a chunk holds as many sources as fit with the widest
+// neighbour closure, each chunk has its own closure, and a row two chunks need is solved in
+// both. OPENR_SPF_ROUTES_CHUNK (tests) forces a chunk size in sources. *solved = rows solved:
+// every source of the batch (a duplicate is solved again, as openr_spf_routes does) plus
+// every chunk's other needed nodes.
+int lfa_on_device(openr_spf_ctx* ctx, Device& d, const uint32_t* d_sources, uint32_t n, uint32_t flags,
+                  const DevGroups& gr, const LfaOut& out, hipStream_t s, uint64_t* total, uint64_t* solved_out) {
+  const uint32_t V = ctx->V, G = gr.n;
+  const uint32_t nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
+  if (out.nhb < nb) return fail(OPENR_SPF_EINVAL, "nh_bytes %u below the graph's next-hop width %u", out.nhb, nb);
+  *total = 0;
+  *solved_out = 0;
+  unsigned long long* ptr = reinterpret_cast<unsigned long long*>(out.ptr);
+  if (!n || !G) {
+    if (out.entries) {
+      HIP_TRY(hipMemsetAsync(ptr, 0, sizeof(unsigned long long), s));
+      HIP_TRY(hipStreamSynchronize(s));
+    }
+    return OPENR_SPF_OK;
+  }
+  Plan plan;
+  int rc = make_plan(ctx, flags & OPENR_SPF_USE_LINK_METRIC, false, &plan);
+  if (rc) return rc;
+  const size_t row_bytes = (size_t)V * 8u, nh_row_bytes = (size_t)V * nb;
+  uint32_t chunk = n;
+  if ((size_t)V * row_bytes + (size_t)n * nh_row_bytes > kWhatifChunkBytes)
+    chunk = (uint32_t)std::min<size_t>(
+        n, std::max<size_t>(1, kWhatifChunkBytes / (row_bytes * ((size_t)ctx->nh_bits + 1u) + nh_row_bytes)));
+  if (const char* e = std::getenv("OPENR_SPF_ROUTES_CHUNK"))
+    if (std::atoi(e) > 0) chunk = std::min<uint32_t>(chunk, (uint32_t)std::atoi(e));
+  const uint32_t words = (V + 31u) / 32u;
+  const size_t E1 = std::max<uint32_t>(ctx->E, 1u);
+  HIP_TRY(d.lf_need.reserve(words));
+  HIP_TRY(d.lf_srcbm.reserve(words));
+  HIP_TRY(d.lf_cnt.reserve(words));
+  HIP_TRY(d.lf_wptr.reserve((size_t)words + 1u));
+  HIP_TRY(d.lf_tsum.reserve(std::max<size_t>(words, (size_t)chunk * G) / 4096u + 1u));
+  HIP_TRY(d.lf_list.reserve(V));
+  HIP_TRY(d.lf_rowidx.reserve(V));
+  HIP_TRY(d.lf_trow.reserve(E1));
+  HIP_TRY(d.lf_ttome.reserve(E1));
+  HIP_TRY(d.lf_tfrom.reserve(E1));
+  HIP_TRY(d.base_nh.reserve((size_t)chunk * nh_row_bytes));
+  HIP_TRY(d.ovf.reserve((size_t)std::max(chunk, V) * ctx->nsl_max()));
+  HIP_TRY(d.rt_large.reserve(routes_reduce_scratch_words(G)));
+  HIP_TRY(reserve_counters(d));
+  // the emit pass reads nh and the scan reads n_alt: library scratch where the caller passed none
+  uint8_t* nh_out = out.nh;
+  uint32_t* nalt_out = out.n_alt;
+  const bool own_nh = out.entries && !nh_out, own_nalt = out.entries && !nalt_out;  // one chunk's worth
+  if (own_nh) {
+    HIP_TRY(d.lf_nh.reserve((size_t)chunk * G * out.nhb));
+    nh_out = d.lf_nh.p;
+  }
+  if (own_nalt) {
+    HIP_TRY(d.lf_nalt.reserve((size_t)chunk * G));
+    nalt_out = d.lf_nalt.p;
+  }
+  unsigned long long carry = 0;
+  uint64_t solved = 0;
+  bool over = false;
+  for (uint32_t c0 = 0; c0 < n; c0 += chunk) {
+    const uint32_t m = std::min(chunk, n - c0);
+    const uint32_t* src = d_sources + c0;
+    const size_t o = (size_t)c0 * G, mg = (size_t)m * G;
+    // 1. the rows the chunk needs
+    HIP_TRY(launch_lfa_rows(d.g, src, m, d.lf_need.p, d.lf_srcbm.p, d.lf_cnt.p, d.lf_tsum.p, d.lf_wptr.p,
+                            d.lf_list.p, d.lf_rowidx.p, d.num_cus, s));
+    unsigned long long extra64 = 0;
+    HIP_TRY(hipMemcpyAsync(&extra64, d.lf_wptr.p + words, sizeof(extra64), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint32_t extra = (uint32_t)std::min<unsigned long long>(extra64, V);
+    // 2. the solves: rows [0, m) the sources (distances and next hops), [m, m + extra) the rest
+    HIP_TRY(d.base_dist.reserve(((size_t)m + extra) * V));
+    SolveArgs a{};
+    a.sources = src;
+    a.n = m;
+    a.dist = d.base_dist.p;
+    a.nh = d.base_nh.p;
+    a.nh_bytes = nb;
+    a.nh_bits = ctx->nh_bits;
+    a.ovf_list = d.ovf.p;
+    a.work = d.work.p;
+    HIP_TRY(launch(ctx, d, plan, a, s));
+    if (extra) {
+      SolveArgs b{};
+      b.sources = d.lf_list.p;
+      b.n = extra;
+      b.dist = d.base_dist.p + (size_t)m * V;
+      b.nh_bytes = nb;
+      b.nh_bits = ctx->nh_bits;
+      b.ovf_list = d.ovf.p;
+      b.work = d.work.p;
+      HIP_TRY(launch(ctx, d, plan, b, s));
+    }
+    solved += (uint64_t)m + extra;
+    // 3. the shortest-path half, the neighbour table, the count pass
+    uint8_t* c_nh = nh_out ? (own_nh ? nh_out : nh_out + o * out.nhb) : nullptr;
+    uint32_t* c_nalt = nalt_out ? (own_nalt ? nalt_out : nalt_out + o) : nullptr;
+    HIP_TRY(launch_routes_reduce(m, V, G, gr.m, gr.ptr, gr.nodes, d.base_dist.p, d.base_nh.p, nb, out.metric + o,
+                                 c_nh, out.nhb, nullptr, d.rt_large.p, d.num_cus, s));
+    HIP_TRY(launch_lfa_table(d.g, src, m, d.lf_rowidx.p, d.base_dist.p, d.lf_trow.p, d.lf_ttome.p, d.lf_tfrom.p,
+                             d.num_cus, s));
+    LfaPass p{};
+    p.n = m;
+    p.V = V;
+    p.G = G;
+    p.M = gr.m;
+    p.onb = out.nhb;
+    p.sources = src;
+    p.row2 = d.g.row2;
+    p.gptr = gr.ptr;
+    p.gnodes = gr.nodes;
+    p.dist = reinterpret_cast<const unsigned long long*>(d.base_dist.p);
+    p.trow = d.lf_trow.p;
+    p.ttome = d.lf_ttome.p;
+    p.tfrom = d.lf_tfrom.p;
+    p.metric = reinterpret_cast<const unsigned long long*>(out.metric + o);
+    p.nh = c_nh;
+    p.alt = out.alt ? out.alt + o * out.nhb : nullptr;
+    p.nalt = c_nalt;
+    p.large = d.rt_large.p;
+    p.n_large = d.rt_large.p + G;
+    HIP_TRY(launch_lfa_reduce(p, false, d.num_cus, s));
+    if (!out.entries) continue;
+    // 4. this chunk's slice of ptr, the total so far, the cap check, the emit pass
+    HIP_TRY(launch_delta_scan(c_nalt, mg, d.lf_tsum.p, ptr + o, s));
+    unsigned long long tot = 0;
+    HIP_TRY(hipMemcpyAsync(&tot, ptr + o + mg, sizeof(tot), hipMemcpyDeviceToHost, s));
+    HIP_TRY(launch_lfa_ptr_shift(ptr + o, mg + 1u, carry, d.num_cus, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    carry += tot;
+    over |= carry > out.cap;
+    if (over || !tot) continue;
+    p.optr = ptr + o;
+    p.onbr = out.nbr;
+    p.ometric = reinterpret_cast<unsigned long long*>(out.alt_metric);
+    HIP_TRY(launch_lfa_reduce(p, true, d.num_cus, s));
+  }
+  *total = carry;
+  *solved_out = solved;
+  ctx->stats.spf_runs += solved;
+  ctx->stats.batches += 1;
+  if (over)
+    return fail(OPENR_SPF_E2BIG, "%llu alternates, cap %llu (ptr, n_alt, metric, nh and alt are filled, entries are not)",
+                carry, (unsigned long long)out.cap);
+  return OPENR_SPF_OK;
+}
+
+// openr_spf_lfa_routes: sources split in contiguous blocks across the devices, each device's
+// entries appended to the caller's at the running total
+int lfa_host(openr_spf_ctx* ctx, const uint32_t* sources, uint32_t n, uint32_t flags, const openr_spf_groups_t* g,
+             uint64_t* metric, uint8_t* nh, uint8_t* alt, uint32_t nh_bytes, uint32_t* n_alt,
+             openr_spf_lfa_entries_t* ent, uint64_t* out_solved) {
+  clear_launch_trace();
+  if (out_solved) *out_solved = 0;
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  int rc = check_groups_host(ctx, g);
+  if (rc) return rc;
+  if (n && !sources) return fail(OPENR_SPF_EINVAL, "null sources");
+  if (n && g->n_groups && !metric) return fail(OPENR_SPF_EINVAL, "null metric");
+  const uint32_t need = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
+  if (nh_bytes < need) return fail(OPENR_SPF_EINVAL, "nh_bytes %u < required %u", nh_bytes, need);
+  for (uint32_t i = 0; i < n; ++i)
+    if (sources[i] >= ctx->V) return fail(OPENR_SPF_EINVAL, "source %u out of range (V=%u)", sources[i], ctx->V);
+  if (ent && !ent->ptr) return fail(OPENR_SPF_EINVAL, "null entries->ptr");
+  if (ent && ent->cap && (!ent->nbr || !ent->metric)) return fail(OPENR_SPF_EINVAL, "null entries->nbr or metric");
+  if ((rc = check_routes_metric(ctx, flags)) != OPENR_SPF_OK) return rc;
+  const uint32_t G = g->n_groups;
+  if (ent) ent->ptr[0] = 0;
+  if (!n || !G) return OPENR_SPF_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint64_t cap = ent ? ent->cap : 0u;
+  const uint32_t nd = (uint32_t)ctx->devs.size();
+  const uint32_t per = (n + nd - 1) / std::max<uint32_t>(nd, 1);
+  uint64_t solved_total = 0, at = 0;
+  bool over = false;
+  std::vector<uint64_t> ptr;
+  for (uint32_t di = 0; di < nd; ++di) {
+    Device& d = ctx->devs[di];
+    const uint32_t b = std::min(n, di * per), e = std::min(n, b + per), m = e - b;
+    if (!m) continue;
+    const size_t mg = (size_t)m * G, o = (size_t)b * G;
+    HIP_TRY(hipSetDevice(d.ordinal));
+    DevGroups gr;
+    if ((rc = upload_groups(d, g, &gr)) != OPENR_SPF_OK) return rc;
+    const uint64_t room = cap > at ? cap - at : 0;
+    HIP_TRY(d.src.reserve(m));
+    HIP_TRY(d.rt_ometric.reserve(mg));
+    HIP_TRY(d.rt_onh.reserve(mg * nh_bytes));
+    HIP_TRY(d.lf_alt.reserve(mg * nh_bytes));
+    HIP_TRY(d.lf_nalt.reserve(mg));
+    if (ent) {
+      HIP_TRY(d.lf_optr.reserve(mg + 1u));
+      HIP_TRY(d.lf_onbr.reserve(std::max<uint64_t>(room, 1)));
+      HIP_TRY(d.lf_oam.reserve(std::max<uint64_t>(room, 1)));
+    }
+    HIP_TRY(hipMemcpyAsync(d.src.p, sources + b, m * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    LfaOut out;
+    out.metric = reinterpret_cast<uint64_t*>(d.rt_ometric.p);
+    out.nh = d.rt_onh.p;
+    out.alt = d.lf_alt.p;
+    out.nhb = nh_bytes;
+    out.n_alt = d.lf_nalt.p;
+    out.entries = ent != nullptr;
+    out.ptr = reinterpret_cast<uint64_t*>(d.lf_optr.p);
+    out.nbr = d.lf_onbr.p;
+    out.alt_metric = reinterpret_cast<uint64_t*>(d.lf_oam.p);
+    out.cap = room;
+    uint64_t total = 0, solved = 0;
+    rc = lfa_on_device(ctx, d, d.src.p, m, flags, gr, out, d.stream, &total, &solved);
+    if (rc && rc != OPENR_SPF_E2BIG) return rc;
+    over |= rc == OPENR_SPF_E2BIG;
+    solved_total += solved;
+    HIP_TRY(hipMemcpyAsync(metric + o, d.rt_ometric.p, mg * sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+    if (nh) HIP_TRY(hipMemcpyAsync(nh + o * nh_bytes, d.rt_onh.p, mg * nh_bytes, hipMemcpyDeviceToHost, d.stream));
+    if (alt) HIP_TRY(hipMemcpyAsync(alt + o * nh_bytes, d.lf_alt.p, mg * nh_bytes, hipMemcpyDeviceToHost, d.stream));
+    if (n_alt) HIP_TRY(hipMemcpyAsync(n_alt + o, d.lf_nalt.p, mg * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+    if (ent) {
+      ptr.resize(mg + 1);
+      HIP_TRY(hipMemcpyAsync(ptr.data(), d.lf_optr.p, (mg + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+      if (!over && total) {
+        HIP_TRY(hipMemcpyAsync(ent->nbr + at, d.lf_onbr.p, total * 4u, hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipMemcpyAsync(ent->metric + at, d.lf_oam.p, total * 8u, hipMemcpyDeviceToHost, d.stream));
+      }
+    }
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    for (size_t u = 0; ent && u < mg; ++u) ent->ptr[o + u + 1] = at + ptr[u + 1];
+    at += total;
+  }
+  ctx->stats.last_batch_ms =
+      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (out_solved) *out_solved = solved_total;
+  if (ent && (over || at > cap))
+    return fail(OPENR_SPF_E2BIG, "%llu alternates, cap %llu (ptr, n_alt, metric, nh and alt are filled, entries are not)",
+                (unsigned long long)at, (unsigned long long)cap);
+  return OPENR_SPF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1911,6 +2182,11 @@ void openr_spf_destroy(openr_spf_ctx* ctx) {
                       d.rt_large.p, d.rt_ovl.p,   d.rt_bm.p,       d.rt_gptr.p,   d.rt_gnodes.p, d.rt_ochanged.p,
                       d.rt_ogroup.p, d.rt_onbest.p, d.rt_nnh.p,     d.rt_bnh.p,    d.rt_onh.p};
     for (void* p : routes)
+      if (p) (void)hipFree(p);
+    void* lfa[] = {d.lf_need.p,  d.lf_srcbm.p, d.lf_cnt.p,  d.lf_list.p,  d.lf_rowidx.p, d.lf_trow.p,
+                   d.lf_nalt.p,  d.lf_onbr.p,  d.lf_wptr.p, d.lf_tsum.p,  d.lf_ttome.p,  d.lf_tfrom.p,
+                   d.lf_optr.p,  d.lf_oam.p,   d.lf_nh.p,   d.lf_alt.p};
+    for (void* p : lfa)
       if (p) (void)hipFree(p);
     void* sweep[] = {d.base_dist.p, d.base_tight.p, d.wdist.p, d.base_nh.p, d.wnh.p, d.wsrc.p, d.wlink.p,
                      d.wunit.p,     d.wcount.p,     d.wiota.p, d.base_tin.p, d.win_links.p, d.win_src.p, d.wchanged.p, d.wchanged_t.p,
@@ -2760,6 +3036,58 @@ int openr_spf_whatif_routes_device(openr_spf_ctx* ctx, int device_index, const u
   rc = whatif_routes_on_device(ctx, d, device_sets(d_set_ptr, d_set_links, n_sets, n_set_links), d_sources, n_sources,
                                flags, gr, d_changed_routes, d_ptr, d_group, d_metric, d_nh, d_n_best, cap, nh_bytes,
                                stream ? reinterpret_cast<hipStream_t>(stream) : d.stream, &total, &solved);
+  if (out_total) *out_total = total;
+  if (out_solved) *out_solved = solved;
+  return rc;
+}
+
+int openr_spf_lfa_routes(openr_spf_ctx* ctx, const uint32_t* sources, uint32_t n, uint32_t flags,
+                         const openr_spf_groups_t* groups, uint64_t* metric, uint8_t* nh, uint8_t* alt,
+                         uint32_t nh_bytes, uint32_t* n_alt, openr_spf_lfa_entries_t* entries,
+                         uint64_t* out_solved) {
+  return lfa_host(ctx, sources, n, flags, groups, metric, nh, alt, nh_bytes, n_alt, entries, out_solved);
+}
+
+int openr_spf_lfa_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_sources, uint32_t n,
+                                uint32_t flags, const uint32_t* d_group_ptr, const uint32_t* d_group_nodes,
+                                uint32_t n_groups, uint32_t n_group_nodes, uint64_t* d_metric, uint8_t* d_nh,
+                                uint8_t* d_alt, uint32_t nh_bytes, uint32_t* d_n_alt, uint64_t* d_ptr,
+                                uint32_t* d_nbr, uint64_t* d_alt_metric, uint64_t cap, void* stream,
+                                uint64_t* out_total, uint64_t* out_solved) {
+  clear_launch_trace();
+  if (out_total) *out_total = 0;
+  if (out_solved) *out_solved = 0;
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (device_index < 0 || device_index >= (int)ctx->devs.size())
+    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+  if ((n && !d_sources) || (n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes) ||
+      (n && n_groups && !d_metric))
+    return fail(OPENR_SPF_EINVAL, "null sources, groups or metric");
+  if (cap && (!d_ptr || !d_nbr || !d_alt_metric)) return fail(OPENR_SPF_EINVAL, "null entry buffer");
+  int rc = check_routes_metric(ctx, flags);
+  if (rc) return rc;
+  Device& d = ctx->devs[device_index];
+  HIP_TRY(hipSetDevice(d.ordinal));
+  DevGroups gr;
+  gr.ptr = d_group_ptr;
+  gr.nodes = d_group_nodes;
+  gr.n = n_groups;
+  gr.m = n_group_nodes;
+  LfaOut out;
+  out.metric = d_metric;
+  out.nh = d_nh;
+  out.alt = d_alt;
+  out.nhb = nh_bytes;
+  out.n_alt = d_n_alt;
+  out.entries = d_ptr != nullptr;
+  out.ptr = d_ptr;
+  out.nbr = d_nbr;
+  out.alt_metric = d_alt_metric;
+  out.cap = cap;
+  uint64_t total = 0, solved = 0;
+  rc = lfa_on_device(ctx, d, d_sources, n, flags, gr, out, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream,
+                     &total, &solved);
   if (out_total) *out_total = total;
   if (out_solved) *out_solved = solved;
   return rc;

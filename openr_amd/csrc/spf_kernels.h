@@ -353,6 +353,59 @@ struct RoutesSweepLayout {
 RoutesSweepLayout whatif_routes_layout(uint32_t V, uint32_t G, size_t units, int num_cus);
 hipError_t launch_whatif_routes(const RoutesSweep& p, const RoutesSweepLayout& l, bool emit, hipStream_t s);
 
+// Boundary between routes_reduce's lane-per-group and wave-per-group kernels (16;
+// OPENR_SPF_ROUTES_SMALL_MAX moves it for the tests). The LFA pass splits at the same size.
+uint32_t routes_small_max();
+
+// Loop-free alternates over prefix groups (spf_lfa.hip): the LFA half of
+// getNextHopsWithMetric (Decision.cpp:1169-1204) on solved rows; the rule is in that file's
+// header and at openr_spf_lfa_routes.
+// launch_lfa_rows: the rows a batch of n sources needs besides the sources' own are the up
+// neighbours that are no source: list[0 .. wptr[ceil(V / 32)]) (device count, nodes
+// ascending) and rowidx[v] = the distance row of every needed node v (a source: its
+// position in the batch; else n + its rank in list). need / srcbm / cnt hold ceil(V / 32)
+// u32, wptr one more u64, tsum one u64 per 4096 words, list and rowidx V u32.
+hipError_t launch_lfa_rows(const DevGraph& g, const uint32_t* sources, uint32_t n, uint32_t* need, uint32_t* srcbm,
+                           uint32_t* cnt, unsigned long long* tsum, unsigned long long* wptr, uint32_t* list,
+                           uint32_t* rowidx, int num_cus, hipStream_t s);
+// The neighbour table ([E] each, a source's row at the CSR offset of its edges): entry b of
+// source s = (distance row of its b-th distinct neighbour n or 0xFFFFFFFF when no link s-n
+// is up, toMe = dist_n(s), dist_s(n)). dist holds the rows rowidx addresses, row i = source i.
+hipError_t launch_lfa_table(const DevGraph& g, const uint32_t* sources, uint32_t n, const uint32_t* rowidx,
+                            const uint64_t* dist, uint32_t* trow, unsigned long long* ttome,
+                            unsigned long long* tfrom, int num_cus, hipStream_t s);
+// The pass over units u = i * G + k (source i, group k). Count pass: alt [n][G][onb]
+// (nullable) and nalt [n][G] = popcount(alt) (nullable). Emit pass: (onbr, ometric) of every
+// set bit from optr[u] on, bits ascending, nothing at or past optr[u + 1]. metric / nh are
+// the routes routes_reduce wrote for the same rows (nh with onb bytes per route; read by the
+// emit pass only), large / n_large the scratch it left (routes_reduce_scratch_words).
+struct LfaPass {
+  uint32_t n, V, G, M, onb;
+  uint32_t small_max, slice;  // set by the launcher (routes_small_max, lfa_slice)
+  const uint32_t* sources;
+  const uint2* row2;
+  const uint32_t* gptr;
+  const uint32_t* gnodes;
+  const unsigned long long* dist;
+  const uint32_t* trow;
+  const unsigned long long* ttome;
+  const unsigned long long* tfrom;
+  const unsigned long long* metric;
+  const uint8_t* nh;
+  uint8_t* alt;
+  uint32_t* nalt;
+  const unsigned long long* optr;
+  uint32_t* onbr;
+  unsigned long long* ometric;
+  const uint32_t* large;
+  const uint32_t* n_large;
+};
+uint32_t lfa_slice();  // neighbours staged in LDS at a time (256; OPENR_SPF_LFA_SLICE)
+hipError_t launch_lfa_reduce(const LfaPass& p, bool emit, int num_cus, hipStream_t s);
+// ptr[0 .. n) += carry (a chunk's scanned counts moved behind the chunks before it)
+hipError_t launch_lfa_ptr_shift(unsigned long long* ptr, size_t n, unsigned long long carry, int num_cus,
+                                hipStream_t s);
+
 // Incremental mirror updates (spf_update.hip).
 // In-place attribute patch of the device mirror: each record overwrites one element of
 // one DevGraph array (structure — rows, columns, link ids — never changes).

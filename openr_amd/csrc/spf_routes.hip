@@ -1,5 +1,7 @@
 // spf_routes.hip — route-level results: best-path selection over prefix groups and the
-// route-level what-if pass (openr_spf_routes*, openr_spf_whatif_routes*).
+// route-level what-if pass (openr_spf_routes*, openr_spf_whatif_routes*). The other half of
+// next-hop selection, loop-free alternates (Decision.cpp:1169-1204), is spf_lfa.hip
+// (openr_spf_lfa_routes*), which runs on the routes this file reduces.
 //
 // A prefix is advertised by a group of nodes (anycast). Its route at a source is
 //   metric = min dist[v] over the members in the SpfResult,
@@ -331,14 +333,18 @@ __global__ __launch_bounds__(64) void whatif_routes_kernel(RoutesSweep p) {
 
 uint32_t routes_reduce_scratch_words(uint32_t G) { return G + 1u; }
 
+uint32_t routes_small_max() {
+  // groups above this size get a wave; OPENR_SPF_ROUTES_SMALL_MAX (tests) moves the boundary
+  if (const char* e = std::getenv("OPENR_SPF_ROUTES_SMALL_MAX")) return (uint32_t)std::strtoul(e, nullptr, 10);
+  return 16u;
+}
+
 hipError_t launch_routes_reduce(uint32_t n, uint32_t V, uint32_t G, uint32_t M, const uint32_t* gptr,
                                 const uint32_t* gnodes, const uint64_t* dist, const uint8_t* nh, uint32_t nb,
                                 uint64_t* metric, uint8_t* onh, uint32_t onb, uint32_t* nbest, uint32_t* scratch,
                                 int num_cus, hipStream_t s) {
   if (!n || !G) return hipSuccess;
-  // groups above this size get a wave; OPENR_SPF_ROUTES_SMALL_MAX (tests) moves the boundary
-  uint32_t small_max = 16u;
-  if (const char* e = std::getenv("OPENR_SPF_ROUTES_SMALL_MAX")) small_max = (uint32_t)std::strtoul(e, nullptr, 10);
+  const uint32_t small_max = routes_small_max();
   uint32_t* n_large = scratch + G;
   hipError_t err = hipMemsetAsync(n_large, 0, sizeof(uint32_t), s);
   if (err != hipSuccess) return err;

@@ -54,6 +54,8 @@ EXPORTS = (
     "openr_spf_routes_device",
     "openr_spf_whatif_routes",
     "openr_spf_whatif_routes_device",
+    "openr_spf_lfa_routes",
+    "openr_spf_lfa_routes_device",
     "openr_spf_ksp2",
     "openr_spf_ksp2_device",
     "openr_spf_host_alloc",
@@ -132,6 +134,15 @@ class WhatifRoutes(ctypes.Structure):  # openr_spf_whatif_routes_t
     ]
 
 
+class LfaEntries(ctypes.Structure):  # openr_spf_lfa_entries_t
+    _fields_ = [
+        ("ptr", ctypes.c_void_p),
+        ("nbr", ctypes.c_void_p),
+        ("metric", ctypes.c_void_p),
+        ("cap", ctypes.c_uint64),
+    ]
+
+
 class SpfLimits(ctypes.Structure):
     _fields_ = [("max_nodes", ctypes.c_uint32), ("max_nh_bits", ctypes.c_uint32)]
 
@@ -195,6 +206,11 @@ def load_library():
     l.openr_spf_whatif_routes_device.argtypes = [vp, ctypes.c_int, vp, vp, u32, u32, vp, u32, u32, vp, vp, u32, u32,
                                                  vp, vp, vp, vp, vp, vp, ctypes.c_uint64, u32, vp,
                                                  P(ctypes.c_uint64), P(ctypes.c_uint64)]
+    l.openr_spf_lfa_routes.argtypes = [vp, vp, u32, u32, P(SpfGroups), vp, vp, vp, u32, vp, P(LfaEntries),
+                                       P(ctypes.c_uint64)]
+    l.openr_spf_lfa_routes_device.argtypes = [vp, ctypes.c_int, vp, u32, u32, vp, vp, u32, u32, vp, vp, vp, u32, vp,
+                                              vp, vp, vp, ctypes.c_uint64, vp, P(ctypes.c_uint64),
+                                              P(ctypes.c_uint64)]
     l.openr_spf_ksp2.argtypes = [vp, vp, vp, u32, u32, vp, vp]
     l.openr_spf_ksp2_device.argtypes = [vp, ctypes.c_int, vp, u32, vp, vp, u32, u32, vp, vp, vp]
     l.openr_spf_host_alloc.argtypes = [ctypes.c_size_t, P(vp)]
@@ -553,6 +569,66 @@ class SpfEngine:
             vp(d_sources), n_sources, flags, vp(d_group_ptr or None), vp(d_group_nodes or None), n_groups,
             n_group_nodes, vp(d_changed), vp(d_ptr), vp(d_group or None), vp(d_metric or None), vp(d_nh or None),
             vp(d_n_best or None), cap, nh_bytes, vp(stream or None), ctypes.byref(total), ctypes.byref(solved))
+        if not (allow_overflow and rc == E2BIG):
+            _check(rc)
+        return int(total.value), int(solved.value)
+
+    def lfa_routes(self, sources: Sequence[int], groups: Sequence[Sequence[int]], use_link_metric: bool = True,
+                   want_entries: bool = True, cap: Optional[int] = None, nh_bytes: Optional[int] = None):
+        """Routes with their loop-free alternates (openr_spf_lfa_routes): (metric[n, G] u64,
+        nh[n, G, nh_bytes] u8, alt[n, G, nh_bytes] u8, n_alt[n, G] u32, ptr[n * G + 1] u64 | None,
+        nbr u32 | None, alt_metric u64 | None, rows solved). metric / nh are the routes of
+        ``routes``; bit b of alt is set iff the source's b-th distinct neighbour (an up link to
+        it) is a loop-free alternate for the group: some member d has dist_n(d) < metric +
+        dist_n(source). Unit u = i * G + k owns entries [ptr[u], ptr[u + 1]): the set bits of alt
+        ascending, each with the distance the reference keeps for that next hop. cap None:
+        sized from a counts-only call."""
+        gp, gn = _ignore_arrays(groups, len(groups))
+        gs = SpfGroups(len(groups), _p(gp), _p(gn))
+        src = np.ascontiguousarray(sources, dtype=np.uint32)
+        n, G = int(src.shape[0]), len(groups)
+        nb = self.nh_bytes if nh_bytes is None else nh_bytes
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        metric = np.zeros((n, G), dtype=np.uint64)
+        nh = np.zeros((n, G, nb), dtype=np.uint8)
+        alt = np.zeros((n, G, nb), dtype=np.uint8)
+        n_alt = np.zeros((n, G), dtype=np.uint32)
+        solved = ctypes.c_uint64()
+
+        def call(ent):
+            return self._lib.openr_spf_lfa_routes(self._ctx, _p(src), n, flags, ctypes.byref(gs), _p(metric), _p(nh),
+                                                  _p(alt), nb, _p(n_alt), ent, ctypes.byref(solved))
+
+        if not want_entries:
+            _check(call(None))
+            return metric, nh, alt, n_alt, None, None, None, int(solved.value)
+        if cap is None:
+            _check(call(None))
+            cap = int(n_alt.sum(dtype=np.uint64))
+        ptr = np.zeros(n * G + 1, dtype=np.uint64)
+        nbr = np.zeros(max(cap, 1), dtype=np.uint32)
+        am = np.zeros(max(cap, 1), dtype=np.uint64)
+        ent = LfaEntries(_p(ptr), _p(nbr), _p(am), cap)
+        _check(call(ctypes.byref(ent)))
+        k = int(ptr[-1])
+        return metric, nh, alt, n_alt, ptr, nbr[:k], am[:k], int(solved.value)
+
+    def lfa_routes_device(self, d_sources: int, n: int, d_group_ptr: int, d_group_nodes: int, n_groups: int,
+                          n_group_nodes: int, d_metric: int, d_nh: int = 0, d_alt: int = 0, nh_bytes: int = 0,
+                          d_n_alt: int = 0, d_ptr: int = 0, d_nbr: int = 0, d_alt_metric: int = 0, cap: int = 0,
+                          use_link_metric: bool = True, stream: int = 0, device_index: int = 0,
+                          allow_overflow: bool = False) -> Tuple[int, int]:
+        """Device-pointer form (openr_spf_lfa_routes_device): (total entries, rows solved).
+        d_ptr 0: no entry output. Synchronizes ``stream`` (see the header)."""
+        vp = ctypes.c_void_p
+        total = ctypes.c_uint64()
+        solved = ctypes.c_uint64()
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        rc = self._lib.openr_spf_lfa_routes_device(
+            self._ctx, device_index, vp(d_sources), n, flags, vp(d_group_ptr or None), vp(d_group_nodes or None),
+            n_groups, n_group_nodes, vp(d_metric), vp(d_nh or None), vp(d_alt or None), nh_bytes or self.nh_bytes,
+            vp(d_n_alt or None), vp(d_ptr or None), vp(d_nbr or None), vp(d_alt_metric or None), cap,
+            vp(stream or None), ctypes.byref(total), ctypes.byref(solved))
         if not (allow_overflow and rc == E2BIG):
             _check(rc)
         return int(total.value), int(solved.value)
