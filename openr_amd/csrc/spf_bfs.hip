@@ -100,7 +100,7 @@ __host__ __device__ inline BfsLayout bfs_layout(uint32_t V, uint32_t L, bool has
 // slice.
 template <int FB, int BLOCK, bool SLICED, bool GENERIC>
 __device__ __forceinline__ void write_out(const SolveArgs& a, uint32_t k, uint32_t sid, uint32_t slice, uint32_t V,
-                                          const uint32_t* st, bool nt) {
+                                          const uint32_t* st) {
   using S = State<FB>;
   const uint32_t tid = threadIdx.x;
   uint64_t* drow = a.dist + out_row_of(a, sid) * V;
@@ -119,13 +119,13 @@ __device__ __forceinline__ void write_out(const SolveArgs& a, uint32_t k, uint32
   if (!nrow) return;
   if (SLICED) {  // the slice's 29-bit chunks, coalesced; slice_merge packs the bytes
     uint32_t* trow = a.slice_tmp + ((size_t)(k - a.k0) * a.nsl + slice) * V;  // chunk-local row
-    for (uint32_t v = tid; v < V; v += BLOCK) store_row<uint32_t>(&trow[v], S::field(st, v) >> S::kNhs, nt);
+    for (uint32_t v = tid; v < V; v += BLOCK) store_row<kNtCodeRows, uint32_t>(&trow[v], S::field(st, v) >> S::kNhs);
     return;
   }
   if (FB == 8 && nb == 1 && ((reinterpret_cast<uintptr_t>(nrow) | V) & 3u) == 0) {
     // four nodes (one state dword) per lane -> one u32 of four next-hop bytes
     uint32_t* n32 = reinterpret_cast<uint32_t*>(nrow);
-    for (uint32_t i = tid; i < V / 4u; i += BLOCK) store_row<uint32_t>(&n32[i], (st[i] >> 3) & 0x1F1F1F1Fu, nt);
+    for (uint32_t i = tid; i < V / 4u; i += BLOCK) store_row<kNtCodeRows, uint32_t>(&n32[i], (st[i] >> 3) & 0x1F1F1F1Fu);
     return;
   }
   for (uint32_t i = tid; i < V * nb; i += BLOCK) {
@@ -148,7 +148,7 @@ __device__ __forceinline__ void write_out(const SolveArgs& a, uint32_t k, uint32
 template <int FB, int BLOCK, bool RING, int ELLM, bool GENERIC, bool SLICED>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BLOCK >= 1024 ? 4 : 8))) void bfs_code_kernel(
     DevGraph g, SolveArgs a, uint64_t cost, uint32_t glog, uint32_t has_ign_rt, uint32_t ring_cap, uint32_t from_list,
-    uint32_t* ctr, uint32_t* ovf_count, uint32_t nt) {
+    uint32_t* ctr, uint32_t* ovf_count) {
   using S = State<FB>;
   constexpr int K = (int)kBfsEdgesPerLane;
   const bool has_ign = GENERIC && has_ign_rt != 0;
@@ -606,7 +606,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BLOCK >= 
 #ifdef OPENR_SPF_PROFILE
         OPENR_PROF_STAMP(t0);
 #endif
-        write_out<FB, BLOCK, SLICED, GENERIC>(a, k, sid, slice, V, st, nt != 0);
+        write_out<FB, BLOCK, SLICED, GENERIC>(a, k, sid, slice, V, st);
 #ifdef OPENR_SPF_PROFILE
         OPENR_PROF_STAMP(t1);
         OPENR_PROF_ADD(6, t0, t1);
@@ -688,7 +688,7 @@ hipError_t launch_bfs_variant(const DevGraph& g, const SolveArgs& a, uint64_t co
   }
   note_launch(RING ? "bfs_code_kernel<ring>" : from_list ? "bfs_code_kernel<full>:rerun" : "bfs_code_kernel<full>");
   hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), lds, s, g, a, cost, glog, (uint32_t)has_ign, ring_cap,
-                     (uint32_t)from_list, ctr, ovf_count, nt_stores());
+                     (uint32_t)from_list, ctr, ovf_count);
   return hipGetLastError();
 }
 
@@ -827,7 +827,7 @@ __host__ __device__ inline WideLayout wide_layout(uint32_t V, uint32_t nw) {
 
 template <int BLOCK, uint32_t NW>
 __global__ __launch_bounds__(BLOCK) void bfs_wide_kernel(DevGraph g, SolveArgs a, uint64_t cost, uint32_t glog,
-                                                         uint32_t nw, uint32_t* ctr, uint32_t nt) {
+                                                         uint32_t nw, uint32_t* ctr) {
   using S = State<32>;
   constexpr int K = (int)kBfsEdgesPerLane;
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -988,7 +988,7 @@ __global__ __launch_bounds__(BLOCK) void bfs_wide_kernel(DevGraph g, SolveArgs a
           const uint32_t p = 4u * i, v = p / nb, j = p - v * nb, n0 = min(4u, nb - j);
           uint32_t x = bits32(v, 8u * j + S::kNhs);
           if (n0 < 4u) x = (x & ((1u << (8u * n0)) - 1u)) | (bits32(v + 1u, S::kNhs) << (8u * n0));
-          store_row<uint32_t>(&n32[i], x, nt != 0);
+          store_row<kNtCodeRows, uint32_t>(&n32[i], x);
         }
       } else {
         for (uint32_t i = tid; i < row_bytes; i += BLOCK) {
@@ -1023,7 +1023,7 @@ hipError_t launch_wide_nw(const DevGraph& g, const SolveArgs& a, uint64_t cost, 
     info->kernel = "bfs_wide_kernel";
   }
   note_launch("bfs_wide_kernel");
-  hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), lds, s, g, a, cost, glog, nw, class_counters(a), nt_stores());
+  hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), lds, s, g, a, cost, glog, nw, class_counters(a));
   return hipGetLastError();
 }
 

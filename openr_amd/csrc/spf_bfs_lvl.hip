@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "spf_bfs_common.h"
 #include "spf_device.h"
@@ -74,22 +75,113 @@ int lvl_class_mode(int cls) {
   }
 }
 
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+
+// u64 distance of a level, all ones when unset, by selects (no branch). SMALL: the cost is
+// below 2^24, so the product is a 24-bit multiply (of a u8 level: it fits the low word).
+template <typename LT, bool SMALL>
+__device__ __forceinline__ uint64_t level_dist(uint32_t l, uint64_t cost) {
+  const bool unset = l == LvlOps<LT>::kUnset;
+  uint32_t lo, hi;
+  if constexpr (SMALL && sizeof(LT) == 1) {
+    lo = __umul24(l, (uint32_t)cost);  // the operands' low 24 bits
+    hi = 0u;
+  } else {
+    const uint64_t x = (uint64_t)l * (SMALL ? (cost & 0xFFFFFFull) : cost);
+    lo = (uint32_t)x;
+    hi = (uint32_t)(x >> 32);
+  }
+  lo = unset ? ~0u : lo;
+  hi = unset ? ~0u : hi;
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// A u64 distance row from the levels in LDS: two nodes per lane and step, one 16-byte
+// store, so a wave's store covers 1 KB of the row without gaps; the LDS reads of eight steps
+// are issued together. (Four nodes per lane from one dword read and two stores, each then
+// covering every other 16 bytes of 2 KB, ran the full batch 5.6 % slower than the loop this
+// replaces: DESIGN.md 5.1, round 8.) AL16 = false: the row base is only 8-byte aligned, so
+// node 0 goes out alone and the pairs start at node 1. The node left past the last pair
+// is stored by one lane.
+template <typename LT, bool NT, bool SMALL, bool AL16>
+__device__ __forceinline__ void dist_row_pairs(uint64_t* drow, uint32_t V, const LT* lvl, uint64_t cost, uint32_t t,
+                                               uint32_t stride) {
+  constexpr uint32_t kBits = 8u * (uint32_t)sizeof(LT), off = AL16 ? 0u : 1u;
+  using Pair = typename std::conditional<sizeof(LT) == 1, uint16_t, uint32_t>::type;
+  const uint32_t np = (V - off) / 2u;  // V >= 1
+  rows_batched<8>(
+      np, t, stride,
+      [&](uint32_t p) -> uint32_t {
+        if constexpr (AL16) return reinterpret_cast<const Pair*>(lvl)[p];
+        return (uint32_t)lvl[2u * p + 1u] | ((uint32_t)lvl[2u * p + 2u] << kBits);
+      },
+      [&](uint32_t p, uint32_t w) {
+        const uint64_t x0 = level_dist<LT, SMALL>(w & LvlOps<LT>::kUnset, cost);
+        const uint64_t x1 = level_dist<LT, SMALL>(w >> kBits, cost);
+        store_row<NT>(reinterpret_cast<u64x2*>(drow + off + 2u * (size_t)p), u64x2{x0, x1});
+      });
+  if (t == 0) {
+    if (!AL16) store_row<NT>(&drow[0], level_dist<LT, SMALL>(lvl[0], cost));
+    const uint32_t v = off + 2u * np;
+    if (v < V) store_row<NT>(&drow[v], level_dist<LT, SMALL>(lvl[v], cost));
+  }
+}
+
+// A next-hop byte row from nibble fields (eight nodes per dword): a lane turns one dword
+// into eight bytes. The row base is 4-byte aligned; AL8: 8-byte aligned (one store).
+template <bool NT, bool AL8, typename NhPtr>
+__device__ __forceinline__ void nh_row_nibbles(uint8_t* nrow, uint32_t V, NhPtr nh, uint32_t t, uint32_t stride) {
+  auto spread = [](uint32_t h) { return (h & 0xFu) | ((h & 0xF0u) << 4) | ((h & 0xF00u) << 8) | ((h & 0xF000u) << 12); };
+  rows_batched<4>(
+      V / 8u, t, stride, [&](uint32_t i) { return (uint32_t)nh[i]; },
+      [&](uint32_t i, uint32_t w) {
+        const u32x2 x = {spread(w & 0xFFFFu), spread(w >> 16)};
+        uint8_t* p = nrow + 8u * (size_t)i;
+        if constexpr (AL8) {
+          store_row<NT>(reinterpret_cast<u32x2*>(p), x);
+        } else {
+          store_row<NT>(reinterpret_cast<uint32_t*>(p), (uint32_t)x.x);
+          store_row<NT>(reinterpret_cast<uint32_t*>(p + 4), (uint32_t)x.y);
+        }
+      });
+  if (t < (V & 7u)) {
+    const uint32_t v = (V & ~7u) + t;
+    nrow[v] = (uint8_t)(((uint32_t)nh[v >> 3] >> (4u * (v & 7u))) & 0xFu);
+  }
+}
+
+// The same from byte fields (four nodes per dword, as stored); 4-byte aligned row base.
+template <bool NT, typename NhPtr>
+__device__ __forceinline__ void nh_row_bytes(uint8_t* nrow, uint32_t V, NhPtr nh, uint32_t t, uint32_t stride) {
+  uint32_t* nrow32 = reinterpret_cast<uint32_t*>(nrow);
+  rows_batched<4>(
+      V / 4u, t, stride, [&](uint32_t i) { return (uint32_t)nh[i]; },
+      [&](uint32_t i, uint32_t w) { store_row<NT>(&nrow32[i], w); });
+  if (t < (V & 3u)) {
+    const uint32_t v = (V & ~3u) + t;
+    nrow[v] = (uint8_t)((uint32_t)nh[v >> 2] >> (8u * (v & 3u)));
+  }
+}
+
 // The distance part of a solve's rows from its levels: u64 distances (level x cost,
 // UINT64_MAX unreached) or, when SolveArgs::lvl_rows is set, the levels themselves (u8 / u16,
 // all ones unreached: the compact form a strong-scaling rank all-gathers),
 // coalesced. Lanes t, t + stride, ... of the writing group.
-template <typename LT>
+template <typename LT, bool NT>
 __device__ __forceinline__ void store_dist_row(const SolveArgs& a, uint32_t sid, uint32_t V, const LT* lvl,
-                                               uint64_t cost, bool nt, uint32_t t, uint32_t stride) {
+                                               uint64_t cost, uint32_t t, uint32_t stride) {
   constexpr uint32_t kUnset = LvlOps<LT>::kUnset;
   const size_t row = out_row_of(a, sid);
   if (a.lvl_rows) {
     if (a.lvl_bytes == 1) {
       uint8_t* lrow = a.lvl_rows + row * V;
-      if (sizeof(LT) == 1 && ((reinterpret_cast<uintptr_t>(lrow) | V) & 3u) == 0) {
+      if (sizeof(LT) == 1 && (reinterpret_cast<uintptr_t>(lrow) & 3u) == 0) {
         const uint32_t* l4 = reinterpret_cast<const uint32_t*>(lvl);  // four u8 levels per dword, as stored
         uint32_t* o4 = reinterpret_cast<uint32_t*>(lrow);
-        for (uint32_t i = t; i < V / 4u; i += stride) store_row<uint32_t>(&o4[i], l4[i], nt);
+        rows_batched<4>(
+            V / 4u, t, stride, [&](uint32_t i) { return l4[i]; },
+            [&](uint32_t i, uint32_t w) { store_row<NT>(&o4[i], w); });
+        if (t < (V & 3u)) lrow[(V & ~3u) + t] = (uint8_t)lvl[(V & ~3u) + t];
       } else {
         bool over = false;
         for (uint32_t v = t; v < V; v += stride) {
@@ -110,26 +202,13 @@ __device__ __forceinline__ void store_dist_row(const SolveArgs& a, uint32_t sid,
     return;
   }
   uint64_t* drow = a.dist + row * V;
-  if (((reinterpret_cast<uintptr_t>(drow) & 15u) | (V & 1u)) == 0) {
-    // two nodes per lane: 16-byte stores
-    ulonglong2* d2 = reinterpret_cast<ulonglong2*>(drow);
-    for (uint32_t i = t; i < V / 2u; i += stride) {
-      const uint32_t l0 = lvl[2u * i], l1 = lvl[2u * i + 1u];
-      const uint64_t x0 = l0 != kUnset ? (uint64_t)l0 * cost : ~0ull;
-      const uint64_t x1 = l1 != kUnset ? (uint64_t)l1 * cost : ~0ull;
-      if (nt) {
-        __builtin_nontemporal_store(x0, &d2[i].x);
-        __builtin_nontemporal_store(x1, &d2[i].y);
-      } else {
-        d2[i] = make_ulonglong2(x0, x1);
-      }
-    }
-  } else {
-    for (uint32_t v = t; v < V; v += stride) {
-      const uint32_t l = lvl[v];
-      store_row<uint64_t>(&drow[v], l != kUnset ? (uint64_t)l * cost : ~0ull, nt);
-    }
-  }
+  const bool al16 = (reinterpret_cast<uintptr_t>(drow) & 15u) == 0;  // uniform, as is the cost
+  if (al16 && cost < (1ull << 24))
+    dist_row_pairs<LT, NT, true, true>(drow, V, lvl, cost, t, stride);
+  else if (al16)
+    dist_row_pairs<LT, NT, false, true>(drow, V, lvl, cost, t, stride);
+  else
+    dist_row_pairs<LT, NT, false, false>(drow, V, lvl, cost, t, stride);
 }
 
 // Writes this solve's dist row (u64, or level row) and next-hop row from LDS, coalesced.
@@ -137,8 +216,9 @@ __device__ __forceinline__ void store_dist_row(const SolveArgs& a, uint32_t sid,
 // distance row and zero-fills the bytes past the last slice.
 template <int MODE, typename LT, int BLOCK, bool SLICED>
 __device__ __forceinline__ void write_rows(const SolveArgs& a, uint32_t sid, uint32_t slice, uint32_t V,
-                                           const LT* lvl, const uint32_t* nh, uint64_t cost, bool nt) {
+                                           const LT* lvl, const uint32_t* nh, uint64_t cost) {
   using N = Nh<MODE>;
+  constexpr bool NT = kNtLvlRows;
   const uint32_t tid = threadIdx.x;
   if (SLICED) {
     if (a.nh) {
@@ -156,22 +236,17 @@ __device__ __forceinline__ void write_rows(const SolveArgs& a, uint32_t sid, uin
     }
     if (slice != 0) return;
   }
-  store_dist_row<LT>(a, sid, V, lvl, cost, nt, tid, (uint32_t)BLOCK);
+  store_dist_row<LT, NT>(a, sid, V, lvl, cost, tid, (uint32_t)BLOCK);
   if (SLICED || !a.nh) return;
   const uint32_t nb = a.nh_bytes;
   uint8_t* nrow = a.nh + out_row_of(a, sid) * V * nb;
-  const bool aligned4 = ((reinterpret_cast<uintptr_t>(nrow) | V) & 3u) == 0;
-  if (MODE == kNhNibble && nb == 1 && aligned4) {
-    // four nodes (four nibbles of one half-dword) per lane -> one u32 of four bytes
-    uint32_t* nrow32 = reinterpret_cast<uint32_t*>(nrow);
-    for (uint32_t i = tid; i < V / 4u; i += BLOCK) {
-      const uint32_t h = (nh[i >> 1] >> ((i & 1u) * 16u)) & 0xFFFFu;
-      store_row<uint32_t>(&nrow32[i], (h & 0xFu) | ((h & 0xF0u) << 4) | ((h & 0xF00u) << 8) | ((h & 0xF000u) << 12),
-                          nt);
-    }
-  } else if (MODE == kNhByte && nb == 1 && aligned4) {
-    uint32_t* nrow32 = reinterpret_cast<uint32_t*>(nrow);
-    for (uint32_t i = tid; i < V / 4u; i += BLOCK) store_row<uint32_t>(&nrow32[i], nh[i], nt);
+  const uint32_t mis = (uint32_t)reinterpret_cast<uintptr_t>(nrow) & 7u;  // uniform
+  if (MODE == kNhNibble && nb == 1 && mis == 0) {
+    nh_row_nibbles<NT, true>(nrow, V, nh, tid, (uint32_t)BLOCK);
+  } else if (MODE == kNhNibble && nb == 1 && mis == 4u) {
+    nh_row_nibbles<NT, false>(nrow, V, nh, tid, (uint32_t)BLOCK);
+  } else if (MODE == kNhByte && nb == 1 && (mis & 3u) == 0) {
+    nh_row_bytes<NT>(nrow, V, nh, tid, (uint32_t)BLOCK);
   } else {
     const uint32_t total = V * nb;
     for (uint32_t i = tid; i < total; i += BLOCK) {
@@ -196,7 +271,6 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8))) void
     DevGraph g, SolveArgs a, uint64_t cost, uint32_t glog, uint32_t has_ign_rt, uint32_t ring_cap, uint32_t from_list,
     uint32_t* ctr, uint32_t* ovf_count, uint32_t flags) {
   constexpr int K = (int)kBfsEdgesPerLane;
-  const uint32_t nt = flags & 1u;
   const bool fresh_lvl = (flags & 2u) != 0;  // level stored by the appending arrival only
   constexpr bool ELECT = Nh<MODE>::kSingle && !SLICED;
   const bool has_ign = GENERIC && has_ign_rt != 0;
@@ -480,7 +554,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8))) void
 #ifdef OPENR_SPF_PROFILE
         OPENR_PROF_STAMP(t0);
 #endif
-        write_rows<MODE, LT, BLOCK, SLICED>(a, sid, slice, V, lvl, nh, cost, nt != 0);
+        write_rows<MODE, LT, BLOCK, SLICED>(a, sid, slice, V, lvl, nh, cost);
 #ifdef OPENR_SPF_PROFILE
         OPENR_PROF_STAMP(t1);
         OPENR_PROF_ADD(6, t0, t1);
@@ -524,7 +598,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8))) void
 struct LeanLayout {
   uint32_t nh, ring, dummy, total;
 };
-constexpr int kLeanProfWords = 11;  // bfs_ell_kernel's OPENR_SPF_PROF counters
+constexpr int kLeanProfWords = 17;  // bfs_ell_kernel's OPENR_SPF_PROF counters
 // [0, 32) control, [32, 32 + V + 4) u8 levels, next-hop words, two queue halves, dummies
 __host__ __device__ inline LeanLayout lean_layout(uint32_t V, uint32_t nh_words, uint32_t ring_cap) {
   LeanLayout l;
@@ -547,7 +621,7 @@ __host__ __device__ inline LeanLayout lean_layout(uint32_t V, uint32_t nh_words,
 // 10 workgroups of 2 waves per CU (5 per SIMD), and 5 is the default since round 6.
 template <int MODE, int BLOCK, bool PROF, bool DELTA, int WPE>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void bfs_ell_kernel(
-    DevGraph g, SolveArgs a, uint64_t cost, uint32_t ring_cap, uint32_t* ctr, uint32_t* ovf_count, uint32_t nt,
+    DevGraph g, SolveArgs a, uint64_t cost, uint32_t ring_cap, uint32_t* ctr, uint32_t* ovf_count,
     unsigned long long* prof) {
   using N = Nh<MODE>;
   static_assert(N::kSingle, "single-dword next-hop fields only");
@@ -577,11 +651,16 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
   // [4] append, [5] drain + barrier; [6] cycles of the narrow runs (hand-back barrier and
   // reload included). A stamp follows an asm use of the value the phase waits for, so it is
   // taken once that value has arrived. Counts (prof[7 ..]): [0] levels, wide and narrow,
-  // [1] solves, [2] narrow levels, [3] narrow runs.
+  // [1] solves, [2] narrow levels, [3] narrow runs. Per-solve phases (prof[11 ..], pacc[7 ..]),
+  // wave 0's cycles between consecutive stamps around the unit loop: [7] claim and source
+  // fetch (from the end-of-unit barrier to the source id's arrival), [8] LDS init, [9] level
+  // 0 up to the first count, [10] the level loop as a whole, [11] row write-out (up to the
+  // last store's issue; the stores' drain falls to the next phase), [12] end of the
+  // write-out to the end-of-unit barrier.
   const bool pf = PROF && prof != nullptr && wave == 0;
-  unsigned long long pacc[7] = {0, 0, 0, 0, 0, 0, 0};
+  unsigned long long pacc[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   uint32_t pcnt[4] = {0, 0, 0, 0};
-  long long ts = 0;
+  long long ts = pf ? (long long)__builtin_amdgcn_s_memtime() : 0, tloop = 0;
 #define OPENR_LEAN_STAMP(i, dep)                             \
   do {                                                       \
     if (pf) {                                                \
@@ -595,6 +674,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
   for (uint32_t unit = blockIdx.x; unit < count;) {
     const uint32_t sid = a.perm ? a.perm[first + unit] : unit;
     const uint32_t src = a.sources[sid];
+    if (pf) OPENR_LEAN_STAMP(7, src);
     if (src < V) {  // block-uniform
       for (uint32_t i = tid; i < lvl_words; i += BLOCK) lvl_w[i] = 0xFFFFFFFFu;
       for (uint32_t i = tid; i < nh_words; i += BLOCK) nh[i] = 0;
@@ -605,6 +685,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         lvl[V] = 0;  // ELL sentinel: level 0 is never > L, so a sentinel slot is never tight
       }
       __syncthreads();
+      if (pf) OPENR_LEAN_STAMP(8, tid);
       // level 0: the source expands even when overloaded; a directly connected node's
       // next hop is the node itself (LinkState.cpp:867-872). Level 1 goes to half 1.
       {
@@ -631,7 +712,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
       uint32_t cur = __builtin_amdgcn_readfirstlane(ctl[1]), L = 1, reached = 1u + cur;
       bool overflow = false;  // block-uniform
       if (pf) {
-        ts = (long long)__builtin_amdgcn_s_memtime();
+        OPENR_LEAN_STAMP(9, cur);
+        tloop = ts;
         pcnt[1] += 1;
       }
       // one lane per frontier node, its K = 4 ELL slots; NPP nodes per wave pass
@@ -812,13 +894,19 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         cur = c;
         if (reached == V) break;  // every node reached: the newest level cannot expand tightly
       }
+      if (pf) {  // the level loop as a whole (its level stamps moved ts)
+        ts = tloop;
+        OPENR_LEAN_STAMP(10, cur);
+      }
       if (overflow) {
         if (tid == 0) a.ovf_list[atomicAdd(ovf_count, 1u)] = unit;
       } else {
-        write_rows<MODE, uint8_t, BLOCK, false>(a, sid, 0, V, lvl_g, nh_g, cost, nt != 0);
+        write_rows<MODE, uint8_t, BLOCK, false>(a, sid, 0, V, lvl_g, nh_g, cost);
       }
+      if (pf) OPENR_LEAN_STAMP(11, tid);
     }
     __syncthreads();  // every lane is done with this unit's LDS and ctl[7]
+    if (pf) OPENR_LEAN_STAMP(12, tid);
     if (tid == 0) ctl[7] = gridDim.x + atomicAdd(&ctr[0], 1u);
     __syncthreads();
     unit = ctl[7];
@@ -827,6 +915,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
   if (pf && lane == 0) {
     for (int i = 0; i < 7; ++i) atomicAdd(&prof[i], pacc[i]);
     for (int i = 0; i < 4; ++i) atomicAdd(&prof[7 + i], (unsigned long long)pcnt[i]);
+    for (int i = 7; i < 13; ++i) atomicAdd(&prof[4 + i], pacc[i]);
   }
   retire_workgroup(ctr, nullptr);
 }
@@ -889,7 +978,7 @@ hipError_t launch_lvl_variant(const DevGraph& g, const SolveArgs& a, uint64_t co
     info->grid = grid;
     info->kernel = RING ? "bfs_lvl_kernel<ring,u8>" : "bfs_lvl_kernel<full,u16>";
   }
-  const uint32_t flags = nt_stores() | (1u << 1);
+  const uint32_t flags = 1u << 1;
   note_launch(RING ? "bfs_lvl_kernel<ring,u8>" : from_list ? "bfs_lvl_kernel<full,u16>:rerun" : "bfs_lvl_kernel<full,u16>");
   hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), lds, s, g, a, cost, glog, (uint32_t)has_ign, ring_cap,
                      (uint32_t)from_list, ctr, ovf_count, flags);
@@ -926,7 +1015,7 @@ hipError_t launch_lvl_lean(const DevGraph& g, const SolveArgs& a, uint64_t cost,
     if (prof) (void)hipMemsetAsync(prof, 0, kLeanProfWords * sizeof(unsigned long long), s);
   }
   note_launch("bfs_ell_kernel");
-  hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), lds, s, g, a, cost, ring_cap, ctr, ovf_count, nt_stores(), prof);
+  hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), lds, s, g, a, cost, ring_cap, ctr, ovf_count, prof);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && prof) {
     unsigned long long h[kLeanProfWords];
@@ -941,6 +1030,15 @@ hipError_t launch_lvl_lean(const DevGraph& g, const SolveArgs& a, uint64_t cost,
                    "cycles/narrow level %.0f narrow runs/solve=%.1f\n",
                    BLOCK, grid, a.n, solves, (double)levels / sv, h[0] / wl, h[1] / wl, h[2] / wl, h[3] / wl, h[4] / wl,
                    h[5] / wl, (double)nlevels / sv, h[6] / nl, (double)nruns / sv);
+      // h[11..16]: the phases of a solve around its level loop
+      unsigned long long all = 0;
+      for (int i = 11; i < kLeanProfWords; ++i) all += h[i];
+      const double pct = all ? 100.0 / (double)all : 0.0;
+      std::fprintf(stderr,
+                   "bfs_ell_solve: cycles/solve %.0f | claim+fetch %.0f (%.2f%%) init %.0f (%.2f%%) level0 %.0f (%.2f%%) "
+                   "loop %.0f (%.2f%%) write-out %.0f (%.2f%%) end barrier %.0f (%.2f%%)\n",
+                   all / sv, h[11] / sv, h[11] * pct, h[12] / sv, h[12] * pct, h[13] / sv, h[13] * pct, h[14] / sv,
+                   h[14] * pct, h[15] / sv, h[15] * pct, h[16] / sv, h[16] * pct);
     }
   }
   return e;
@@ -980,51 +1078,25 @@ __host__ __device__ inline WaveLayout wave_layout(uint32_t V, uint32_t nh_words,
 // from the slot's u8 levels at LDS byte `slot` (`lvl8`: the same bytes through smem), then the next-hop bytes.
 template <int MODE>
 __device__ __forceinline__ void wave_rows_out(const SolveArgs& a, uint32_t sid, uint32_t V, uint32_t slot,
-                                              const uint8_t* lvl8, const lds_u32* nh, uint64_t cost, bool nt, uint32_t t,
+                                              const uint8_t* lvl8, const lds_u32* nh, uint64_t cost, uint32_t t,
                                               uint32_t stride) {
   using N = Nh<MODE>;
+  constexpr bool NT = kNtLvlRows;
   constexpr uint32_t kBits = 32u / N::kPer;
   constexpr uint32_t kLog = kBits == 4 ? 3 : kBits == 8 ? 2 : kBits == 16 ? 1 : 0;
   constexpr uint32_t kShl = 5u - kLog;
-  const lds_u32* const lvl_w = (const lds_u32*)(size_t)slot;
-  uint64_t* drow = a.dist ? a.dist + out_row_of(a, sid) * V : nullptr;
-  if (!a.lvl_rows && ((reinterpret_cast<uintptr_t>(drow) & 15u) | (V & 3u)) == 0) {
-    ulonglong2* d2 = reinterpret_cast<ulonglong2*>(drow);
-    for (uint32_t i = t; i < V / 4u; i += stride) {
-      const uint32_t w = lvl_w[i];
-      uint64_t xd[4];
-#pragma unroll
-      for (uint32_t k = 0; k < 4u; ++k) {
-        const uint32_t l = (w >> (8u * k)) & 0xFFu;
-        xd[k] = l != 0xFFu ? (uint64_t)l * cost : ~0ull;
-      }
-      if (nt) {
-        __builtin_nontemporal_store(xd[0], &d2[2u * i].x);
-        __builtin_nontemporal_store(xd[1], &d2[2u * i].y);
-        __builtin_nontemporal_store(xd[2], &d2[2u * i + 1u].x);
-        __builtin_nontemporal_store(xd[3], &d2[2u * i + 1u].y);
-      } else {
-        d2[2u * i] = make_ulonglong2(xd[0], xd[1]);
-        d2[2u * i + 1u] = make_ulonglong2(xd[2], xd[3]);
-      }
-    }
-  } else {
-    store_dist_row<uint8_t>(a, sid, V, lvl8, cost, nt, t, stride);
-  }
+  (void)slot;
+  store_dist_row<uint8_t, NT>(a, sid, V, lvl8, cost, t, stride);
   if (!a.nh) return;
   const uint32_t nb = a.nh_bytes;
   uint8_t* nrow = a.nh + out_row_of(a, sid) * V * nb;
-  const bool aligned4 = ((reinterpret_cast<uintptr_t>(nrow) | V) & 3u) == 0;
-  if (MODE == kNhNibble && nb == 1 && aligned4) {
-    uint32_t* nrow32 = reinterpret_cast<uint32_t*>(nrow);
-    for (uint32_t i = t; i < V / 4u; i += stride) {
-      const uint32_t h = (nh[i >> 1] >> ((i & 1u) * 16u)) & 0xFFFFu;
-      store_row<uint32_t>(&nrow32[i], (h & 0xFu) | ((h & 0xF0u) << 4) | ((h & 0xF00u) << 8) | ((h & 0xF000u) << 12),
-                          nt);
-    }
-  } else if (MODE == kNhByte && nb == 1 && aligned4) {
-    uint32_t* nrow32 = reinterpret_cast<uint32_t*>(nrow);
-    for (uint32_t i = t; i < V / 4u; i += stride) store_row<uint32_t>(&nrow32[i], (uint32_t)nh[i], nt);
+  const uint32_t mis = (uint32_t)reinterpret_cast<uintptr_t>(nrow) & 7u;  // uniform
+  if (MODE == kNhNibble && nb == 1 && mis == 0) {
+    nh_row_nibbles<NT, true>(nrow, V, nh, t, stride);
+  } else if (MODE == kNhNibble && nb == 1 && mis == 4u) {
+    nh_row_nibbles<NT, false>(nrow, V, nh, t, stride);
+  } else if (MODE == kNhByte && nb == 1 && (mis & 3u) == 0) {
+    nh_row_bytes<NT>(nrow, V, nh, t, stride);
   } else {
     for (uint32_t i = t; i < V * nb; i += stride) {
       const uint32_t v = i / nb, j = i - v * nb;
@@ -1036,7 +1108,7 @@ __device__ __forceinline__ void wave_rows_out(const SolveArgs& a, uint32_t sid, 
 
 template <int MODE, uint32_t U>
 __global__ __launch_bounds__(512) void bfs_wave_kernel(DevGraph g, SolveArgs a, uint64_t cost, uint32_t qhalf,
-                                                       uint32_t waves, uint32_t* ctr, uint32_t* ovf_count, uint32_t nt) {
+                                                       uint32_t waves, uint32_t* ctr, uint32_t* ovf_count) {
   using N = Nh<MODE>;
   static_assert(N::kSingle, "single-dword next-hop fields only");
   constexpr uint32_t kBits = 32u / N::kPer;
@@ -1165,7 +1237,7 @@ __global__ __launch_bounds__(512) void bfs_wave_kernel(DevGraph g, SolveArgs a, 
       if (overflow) {
         if (lane == 0) a.ovf_list[atomicAdd(ovf_count, 1u)] = unit;
       } else {
-        wave_rows_out<MODE>(a, sid, V, slot, reinterpret_cast<const uint8_t*>(smem) + slot, nh, cost, nt != 0, lane, 64u);
+        wave_rows_out<MODE>(a, sid, V, slot, reinterpret_cast<const uint8_t*>(smem) + slot, nh, cost, lane, 64u);
       }
     }
     uint32_t nx = 0;
@@ -1211,7 +1283,7 @@ hipError_t launch_lvl_wave(const DevGraph& g, const SolveArgs& a, uint64_t cost,
     info->kernel = "bfs_wave_kernel<lds-graph>";
   }
   note_launch("bfs_wave_kernel");
-  hipLaunchKernelGGL(k, dim3(grid), dim3(64u * waves), lds, s, g, a, cost, qhalf, waves, ctr, ovf_count, nt_stores());
+  hipLaunchKernelGGL(k, dim3(grid), dim3(64u * waves), lds, s, g, a, cost, qhalf, waves, ctr, ovf_count);
   if (prof_enabled())  // tests: which pass ran
     std::fprintf(stderr, "bfs_wave: grid=%u waves=%u n=%u qhalf=%u lds=%u\n", grid, waves, a.n, qhalf, lds);
   return hipGetLastError();

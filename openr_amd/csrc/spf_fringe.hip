@@ -205,7 +205,7 @@ __global__ __launch_bounds__(kWave) void fringe_kernel(DevGraph g, SolveArgs a, 
       uint64_t* drow = a.dist + out_row_of(a, sid) * V;
       for (uint32_t v = lane; v < V; v += kWave) {
         const D d = dist[v];
-        store_row<uint64_t>(&drow[v], d == INF ? ~0ull : (uint64_t)d, true);
+        store_row<true, uint64_t>(&drow[v], d == INF ? ~0ull : (uint64_t)d);
       }
       if (a.nh) {
         const uint32_t nb = a.nh_bytes;
