@@ -32,6 +32,9 @@
  *                              group), from the rows of the sources and their neighbours
  *   openr_spf_whatif_routes    the link-set sweep resolved to routes: per (failure set,
  *                              source) the groups whose route changed, with the new route
+ *   openr_spf_whatif_lfa       the same sweep resolved to LFA RIB entries: per (failure set,
+ *                              source) the groups whose route or alternates changed, and
+ *                              how many are left with a single next hop
  *   openr_spf_ksp2             LinkState::getKthPaths(src, dst, 1 and 2) (LinkState.cpp:762-791)
  *                              for a batch of pairs, paths traced on the device
  *   openr_spf_patch_graph      attribute-only mirror updates (metric, Link::isUp, node
@@ -385,8 +388,8 @@ int openr_spf_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t
    reached only over down links is never tested. An overloaded neighbour is tested (its own
    SPF expands it as the source). A group that contains s has metric 0 and an empty nh, and
    its other members can still qualify a neighbour. The hop-count form applies the same rule
-   to hop rows. perDestination = true (the KSP2 / BGP form), multi-area ECMP and LFA over
-   what-if rows are not covered.
+   to hop rows. perDestination = true (the KSP2 / BGP form) and multi-area ECMP are not
+   covered; the rule over what-if rows is openr_spf_whatif_lfa.
    entries (nullable: no entry output, one pass) is a CSR over units u = i * n_groups + k:
    unit u's alternates are [ptr[u], ptr[u + 1]), next-hop bits ascending. OPENR_SPF_E2BIG
    means sum(n_alt) > cap and nothing else: ptr, n_alt, metric, nh and alt are filled, the
@@ -470,6 +473,74 @@ int openr_spf_whatif_routes_device(openr_spf_ctx* ctx, int device_index, const u
                                    uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh, uint32_t* d_n_best,
                                    uint64_t cap, uint32_t nh_bytes, void* stream, uint64_t* out_total,
                                    uint64_t* out_solved);
+
+/* Post-failure loop-free alternates: which (source, prefix group) pairs keep a backup next
+   hop after a router or a shared-risk group fails, and which lose it. For failure set i (a
+   link set as in openr_spf_whatif_sets), source j (node s) and group k the LFA RIB entry
+   (metric', nh', alt') is exactly what openr_spf_lfa_routes returns for (s, k) on the graph
+   in which every link of set i has edge_up = 0, under the same flags:
+     - metric' and nh' are the route of openr_spf_whatif_routes for that unit. Next-hop bit
+       positions are those of the unfailed graph (openr_spf_neighbor_map): a failure never
+       renumbers bits.
+     - a neighbour n of s is tested iff at least one link s-n is up and not in set i (the
+       reference skips links that are not up in its LFA loop, Decision.cpp:1169-1204).
+     - toMe = dist'_n(s); a member d qualifies when dist'_n(d) != UINT64_MAX and dist'_n(d) <
+       metric' + toMe, primes denoting rows of runSpf(x, useLinkMetric, set i).
+     - alt' is empty when metric' == UINT64_MAX.
+     - every other rule of openr_spf_lfa_routes holds unchanged: every member is tested, an
+       overloaded neighbour is tested, a group holding s has metric 0 and an empty nh, alt and
+       nh are zero past the graph's width.
+   An entry of unit u = i * n_sources + j changed iff metric', nh' or alt' differs from the
+   no-failure entry of (s, k). An empty set changes nothing.
+     changed[i][j]      changed entries of the unit
+     unprotected[i][j]  (nullable) groups that are live after the failure (metric' !=
+                        UINT64_MAX and nh' non-empty) with popcount(nh' | alt') == 1
+     lost_backup[i][j]  (nullable) groups that were live with popcount(nh | alt) >= 2 before
+                        the failure and are live with popcount(nh' | alt') == 1 after it
+   delta (nullable: counts only) is a CSR over units exactly like openr_spf_whatif_routes_t:
+   unit u's entries are [ptr[u], ptr[u + 1]), group ids ascending, each with the new metric,
+   nh and alt (nh_bytes >= the graph's width, zero past it). OPENR_SPF_E2BIG means
+   sum(changed) > cap and nothing else: ptr and all counts are filled, the entries are not;
+   cap = 0 gives counts and ptr only. *out_solved (nullable) is what openr_spf_whatif_sets
+   reports for the same sets over the list "the sources as given, then their up neighbours
+   that are no source, ascending" (the sweep this call runs); it is added to stats.spf_runs.
+   Sets are validated as in openr_spf_whatif_sets, groups and metrics as in openr_spf_routes
+   (EINVAL; ENOTSUP for a usable metric outside [1, 2^31-1] under link metric, the hop-count
+   form is always allowed); nh_bytes below the graph's width is EINVAL. Sets are split in
+   contiguous blocks across the context's devices. Not covered: per-alternate alt_metric
+   entries under failure, perDestination = true, multi-area, and chunking of the sources (the
+   base rows of the sources and their neighbours must fit what the sweep accepts; larger
+   inputs get the sweep's own error). */
+typedef struct {
+  uint64_t* ptr;     /* [n_sets * n_sources + 1] */
+  uint32_t* group;   /* [cap] group ids, ascending inside a unit */
+  uint64_t* metric;  /* [cap] new metric, UINT64_MAX = route lost */
+  uint8_t* nh;       /* [cap][nh_bytes] */
+  uint8_t* alt;      /* [cap][nh_bytes] */
+  uint64_t cap;      /* entries the caller allocated */
+  uint32_t nh_bytes; /* bytes per next-hop entry */
+} openr_spf_whatif_lfa_t;
+int openr_spf_whatif_lfa(openr_spf_ctx* ctx, const uint32_t* set_ptr, const uint32_t* set_links, uint32_t n_sets,
+                         const uint32_t* sources, uint32_t n_sources, uint32_t flags,
+                         const openr_spf_groups_t* groups, uint32_t* changed, uint32_t* unprotected,
+                         uint32_t* lost_backup, openr_spf_whatif_lfa_t* delta, uint64_t* out_solved);
+
+/* Device-buffer form (every buffer device memory). Sets and groups are not validated: they
+   are clamped exactly as in openr_spf_whatif_routes_device and openr_spf_lfa_routes_device (a
+   slice is clamped to its array, a link id >= L matches no link, a member >= V counts as
+   unreached). d_changed [n_sets][n_sources]; d_unprotected and d_lost_backup may be NULL.
+   d_ptr NULL: counts only (the entry buffers and cap are ignored). Else d_ptr [n_units + 1] is
+   always filled, each unit's entries in the order the kernel found them (not sorted); when
+   the total exceeds cap the entries are not written and the call returns OPENR_SPF_E2BIG.
+   *out_total (host, nullable) = sum(changed). Synchronizes `stream`. */
+int openr_spf_whatif_lfa_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_set_ptr,
+                                const uint32_t* d_set_links, uint32_t n_sets, uint32_t n_set_links,
+                                const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                                const uint32_t* d_group_ptr, const uint32_t* d_group_nodes, uint32_t n_groups,
+                                uint32_t n_group_nodes, uint32_t* d_changed, uint32_t* d_unprotected,
+                                uint32_t* d_lost_backup, uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric,
+                                uint8_t* d_nh, uint8_t* d_alt, uint64_t cap, uint32_t nh_bytes, void* stream,
+                                uint64_t* out_total, uint64_t* out_solved);
 
 /* LinkState::getKthPaths(src[i], dst[i], 1) and (.., 2) (LinkState.cpp:762-791, with
    traceOnePath :398-419) for a batch of pairs, traced on the device. Per pair, tok1 /

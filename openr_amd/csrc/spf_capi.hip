@@ -124,6 +124,13 @@ struct Device {
   DevBuf<uint32_t> lf_need, lf_srcbm, lf_cnt, lf_list, lf_rowidx, lf_trow, lf_nalt, lf_onbr;
   DevBuf<unsigned long long> lf_wptr, lf_tsum, lf_ttome, lf_tfrom, lf_optr, lf_oam;
   DevBuf<uint8_t> lf_nh, lf_alt;
+  // post-failure alternates (spf_wlfa.hip): the closure list the sweep runs over, the base
+  // alternates and unprotected counts, the affected-unit list, the bitmap slices when they
+  // are not in LDS, and the host form's outputs before they are copied out (the node delta,
+  // base routes and inverse map share the rt_ buffers, the closure the lf_ ones)
+  DevBuf<uint32_t> wl_clos, wl_bunprot, wl_alist, wl_acount, wl_bm, wl_ochanged, wl_ounprot, wl_olost, wl_ogroup;
+  DevBuf<unsigned long long> wl_optr, wl_ometric;
+  DevBuf<uint8_t> wl_balt, wl_onh, wl_oalt;
   // incremental updates: patch records, the last patch's delta edges, refresh work list,
   // host-form refresh rows
   DevBuf<PatchRec> precs;
@@ -2065,6 +2072,335 @@ int lfa_host(openr_spf_ctx* ctx, const uint32_t* sources, uint32_t n, uint32_t f
   return OPENR_SPF_OK;
 }
 
+// ---- post-failure loop-free alternates (spf_wlfa.hip) ----------------------------------------
+
+// Outputs of openr_spf_whatif_lfa[_device] in device memory. unprot, lost and ptr may be null
+// (ptr null: counts only, the scan goes to library scratch).
+struct WlfaOut {
+  uint32_t* changed = nullptr;
+  uint32_t* unprot = nullptr;
+  uint32_t* lost = nullptr;
+  uint64_t* ptr = nullptr;
+  uint32_t* group = nullptr;
+  uint64_t* metric = nullptr;
+  uint8_t* nh = nullptr;
+  uint8_t* alt = nullptr;
+  uint64_t cap = 0;
+  uint32_t nhb = 0;
+};
+
+// openr_spf_whatif_lfa[_device] on one device: the closure list of the sources
+// (launch_lfa_rows; one synchronization for its length), the link-set sweep over sets x
+// closure with the node delta into library scratch (base rows of every closure node stay
+// resident; the capacity is estimated and the sweep rerun on overflow, as in
+// whatif_routes_on_device), the base routes and base alternates of the sources, the inverse
+// map, the mark pass, the count pass, the scan of the counts, the cap check and the emit
+// pass. OPENR_SPF_E2BIG only ever means sum(changed) > cap. Synchronizes s.
+int whatif_lfa_on_device(openr_spf_ctx* ctx, Device& d, const WhatifUnits& un, const uint32_t* d_sources,
+                         uint32_t n_src, uint32_t flags, const DevGroups& gr, const WlfaOut& out, hipStream_t s,
+                         uint64_t* total, uint64_t* solved_out) {
+  const uint32_t V = ctx->V, G = gr.n;
+  const uint32_t nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
+  if (out.nhb < nb) return fail(OPENR_SPF_EINVAL, "nh_bytes %u below the graph's next-hop width %u", out.nhb, nb);
+  *total = 0;
+  *solved_out = 0;
+  const size_t units = (size_t)un.n * n_src;
+  if (!units || !G) {
+    if (units) {
+      HIP_TRY(hipMemsetAsync(out.changed, 0, units * sizeof(uint32_t), s));
+      if (out.unprot) HIP_TRY(hipMemsetAsync(out.unprot, 0, units * sizeof(uint32_t), s));
+      if (out.lost) HIP_TRY(hipMemsetAsync(out.lost, 0, units * sizeof(uint32_t), s));
+    }
+    if (out.ptr) HIP_TRY(hipMemsetAsync(out.ptr, 0, (units + 1u) * sizeof(uint64_t), s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return OPENR_SPF_OK;
+  }
+  // 1. the rows the sources need: themselves, then their up neighbours that are no source
+  const uint32_t words = (V + 31u) / 32u;
+  const size_t E1 = std::max<uint32_t>(ctx->E, 1u);
+  HIP_TRY(d.lf_need.reserve(words));
+  HIP_TRY(d.lf_srcbm.reserve(words));
+  HIP_TRY(d.lf_cnt.reserve(words));
+  HIP_TRY(d.lf_wptr.reserve((size_t)words + 1u));
+  HIP_TRY(d.lf_tsum.reserve(words / 4096u + 1u));
+  HIP_TRY(d.lf_list.reserve(V));
+  HIP_TRY(d.lf_rowidx.reserve(V));
+  HIP_TRY(d.lf_trow.reserve(E1));
+  HIP_TRY(d.lf_ttome.reserve(E1));
+  HIP_TRY(d.lf_tfrom.reserve(E1));
+  HIP_TRY(launch_lfa_rows(d.g, d_sources, n_src, d.lf_need.p, d.lf_srcbm.p, d.lf_cnt.p, d.lf_tsum.p, d.lf_wptr.p,
+                          d.lf_list.p, d.lf_rowidx.p, d.num_cus, s));
+  unsigned long long extra64 = 0;
+  HIP_TRY(hipMemcpyAsync(&extra64, d.lf_wptr.p + words, sizeof(extra64), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const uint32_t extra = (uint32_t)std::min<unsigned long long>(extra64, V);
+  if ((uint64_t)n_src + extra > 0xFFFFFFFFull) return fail(OPENR_SPF_EINVAL, "too many sources");
+  const uint32_t n_rows = n_src + extra;
+  HIP_TRY(d.wl_clos.reserve(n_rows));
+  HIP_TRY(hipMemcpyAsync(d.wl_clos.p, d_sources, (size_t)n_src * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+  if (extra)
+    HIP_TRY(hipMemcpyAsync(d.wl_clos.p + n_src, d.lf_list.p, (size_t)extra * sizeof(uint32_t),
+                           hipMemcpyDeviceToDevice, s));
+  // 2. the node sweep over sets x closure
+  const size_t nunits = (size_t)un.n * n_rows;
+  HIP_TRY(d.rt_nchanged.reserve(nunits));
+  HIP_TRY(d.rt_nptr.reserve(nunits + 1u));
+  uint64_t ncap = std::min<uint64_t>((uint64_t)nunits * V, std::max<uint64_t>((uint64_t)nunits * 16u, 1u << 20));
+  if (const char* e = std::getenv("OPENR_SPF_ROUTES_DELTA_CAP"))  // tests: start below the total (the rerun)
+    ncap = std::strtoull(e, nullptr, 10);
+  uint64_t ntotal = 0;
+  for (int attempt = 0;; ++attempt) {
+    HIP_TRY(d.rt_nnode.reserve(std::max<uint64_t>(ncap, 1)));
+    HIP_TRY(d.rt_ndist.reserve(std::max<uint64_t>(ncap, 1)));
+    HIP_TRY(d.rt_nnh.reserve(std::max<uint64_t>(ncap * nb, 1)));
+    const openr_spf_stats_t stats0 = ctx->stats;
+    uint64_t pool = 0;
+    const int rc = whatif_delta_on_device(ctx, d, un, d.wl_clos.p, n_rows, flags, d.rt_nchanged.p,
+                                          reinterpret_cast<uint64_t*>(d.rt_nptr.p), d.rt_nnode.p, d.rt_ndist.p,
+                                          d.rt_nnh.p, ncap, nb, s, &ntotal, solved_out, &pool);
+    if (rc == OPENR_SPF_OK) break;
+    if (rc != OPENR_SPF_E2BIG) return rc;
+    if (attempt == 2 || ntotal > (uint64_t)nunits * V)
+      return fail(OPENR_SPF_ENOMEM, "node delta of %llu entries did not fit library scratch",
+                  (unsigned long long)ntotal);
+    ctx->stats = stats0;  // the rerun counts once
+    ncap = std::max<uint64_t>(ntotal, pool / 2u + 1u);
+  }
+  // 3. base routes of the sources (rows [0, n_src) of the closure)
+  const size_t bg = (size_t)n_src * G;
+  HIP_TRY(d.rt_bmetric.reserve(bg));
+  HIP_TRY(d.rt_bnh.reserve(bg * nb));
+  HIP_TRY(d.rt_large.reserve(routes_reduce_scratch_words(G)));
+  HIP_TRY(launch_routes_reduce(n_src, V, G, gr.m, gr.ptr, gr.nodes, d.base_dist.p, d.base_nh.p, nb,
+                               reinterpret_cast<uint64_t*>(d.rt_bmetric.p), d.rt_bnh.p, nb, nullptr, d.rt_large.p,
+                               d.num_cus, s));
+  // 4. base alternates
+  HIP_TRY(d.wl_balt.reserve(bg * nb));
+  HIP_TRY(launch_lfa_table(d.g, d_sources, n_src, d.lf_rowidx.p, d.base_dist.p, d.lf_trow.p, d.lf_ttome.p,
+                           d.lf_tfrom.p, d.num_cus, s));
+  LfaPass lp{};
+  lp.n = n_src;
+  lp.V = V;
+  lp.G = G;
+  lp.M = gr.m;
+  lp.onb = nb;
+  lp.sources = d_sources;
+  lp.row2 = d.g.row2;
+  lp.gptr = gr.ptr;
+  lp.gnodes = gr.nodes;
+  lp.dist = reinterpret_cast<const unsigned long long*>(d.base_dist.p);
+  lp.trow = d.lf_trow.p;
+  lp.ttome = d.lf_ttome.p;
+  lp.tfrom = d.lf_tfrom.p;
+  lp.metric = d.rt_bmetric.p;
+  lp.nh = d.rt_bnh.p;
+  lp.alt = d.wl_balt.p;
+  lp.large = d.rt_large.p;
+  lp.n_large = d.rt_large.p + G;
+  HIP_TRY(launch_lfa_reduce(lp, false, d.num_cus, s));
+  // 5. inverse map node -> groups
+  HIP_TRY(d.rt_icnt.reserve(V));
+  HIP_TRY(d.rt_icur.reserve(V));
+  HIP_TRY(d.rt_iptr.reserve((size_t)V + 1u));
+  HIP_TRY(d.rt_inv.reserve(std::max<uint32_t>(gr.m, 1u)));
+  HIP_TRY(d.rt_tsum.reserve(std::max<size_t>(units, V) / 4096u + 1u));
+  HIP_TRY(launch_routes_inverse(V, G, gr.m, gr.ptr, gr.nodes, d.rt_icnt.p, d.rt_icur.p, d.rt_tsum.p, d.rt_iptr.p,
+                                d.rt_inv.p, d.num_cus, s));
+  // 6. mark pass; 7. count pass, scan, cap check, emit pass
+  const WlfaLayout lay = whatif_lfa_layout(G, units, d.num_cus);
+  HIP_TRY(d.wl_bm.reserve(std::max<size_t>(lay.bm_words, 1)));
+  HIP_TRY(d.wl_bunprot.reserve(n_src));
+  HIP_TRY(d.wl_alist.reserve(units));
+  HIP_TRY(d.wl_acount.reserve(1));
+  unsigned long long* ptr = reinterpret_cast<unsigned long long*>(out.ptr);
+  if (!ptr) {
+    HIP_TRY(d.wl_optr.reserve(units + 1u));
+    ptr = d.wl_optr.p;
+  }
+  WlfaPass p{};
+  p.V = V;
+  p.G = G;
+  p.M = gr.m;
+  p.n_src = n_src;
+  p.n_rows = n_rows;
+  p.n_sets = un.n;
+  p.n_set_links = un.n_set_links;
+  p.nb = nb;
+  p.onb = out.nhb;
+  p.set_ptr = un.set_ptr;
+  p.set_links = un.set_links;
+  p.sources = d_sources;
+  p.row2 = d.g.row2;
+  p.adj = d.g.adj;
+  p.lid = d.g.lid;
+  p.nbr = d.g.nbr;
+  p.rowidx = d.lf_rowidx.p;
+  p.gptr = gr.ptr;
+  p.gnodes = gr.nodes;
+  p.iptr = d.rt_iptr.p;
+  p.inv = d.rt_inv.p;
+  p.nchanged = d.rt_nchanged.p;
+  p.nptr = d.rt_nptr.p;
+  p.nnode = d.rt_nnode.p;
+  p.ndist = d.rt_ndist.p;
+  p.nnh = d.rt_nnh.p;
+  p.bdist = reinterpret_cast<const unsigned long long*>(d.base_dist.p);
+  p.bnh = d.base_nh.p;
+  p.trow = d.lf_trow.p;
+  p.ttome = d.lf_ttome.p;
+  p.bmetric = d.rt_bmetric.p;
+  p.bmnh = d.rt_bnh.p;
+  p.balt = d.wl_balt.p;
+  p.bunprot = d.wl_bunprot.p;
+  p.alist = d.wl_alist.p;
+  p.acount = d.wl_acount.p;
+  p.changed = out.changed;
+  p.unprot = out.unprot;
+  p.lost = out.lost;
+  p.optr = ptr;
+  p.ogroup = out.group;
+  p.ometric = reinterpret_cast<unsigned long long*>(out.metric);
+  p.onh = out.nh;
+  p.oalt = out.alt;
+  p.g_bm = d.wl_bm.p;
+  HIP_TRY(launch_wlfa_mark(p, d.num_cus, s));
+  HIP_TRY(launch_wlfa(p, lay, false, s));
+  HIP_TRY(launch_delta_scan(out.changed, units, d.rt_tsum.p, ptr, s));
+  unsigned long long tot = 0;
+  HIP_TRY(hipMemcpyAsync(&tot, ptr + units, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *total = tot;
+  if (!out.ptr) return OPENR_SPF_OK;  // counts only
+  if (tot > out.cap)
+    return fail(OPENR_SPF_E2BIG, "%llu entries changed, cap %llu (ptr and the counts are filled, entries are not)", tot,
+                (unsigned long long)out.cap);
+  if (tot) {
+    HIP_TRY(launch_wlfa(p, lay, true, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  return OPENR_SPF_OK;
+}
+
+// openr_spf_whatif_lfa: sets split in contiguous blocks across the devices, each device's CSR
+// appended to the caller's at the running total, each unit's entries sorted by group id
+int whatif_lfa_host(openr_spf_ctx* ctx, const WhatifUnits& hu, const uint32_t* sources, uint32_t n_sources,
+                    uint32_t flags, const openr_spf_groups_t* g, uint32_t* changed, uint32_t* unprotected,
+                    uint32_t* lost_backup, openr_spf_whatif_lfa_t* delta, uint64_t* out_solved) {
+  clear_launch_trace();
+  const uint32_t n_sets = hu.n;
+  if (out_solved) *out_solved = 0;
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  int rc = check_whatif_host(ctx, hu, sources, n_sources, changed);
+  if (rc) return rc;
+  if ((rc = check_groups_host(ctx, g)) != OPENR_SPF_OK) return rc;
+  if (delta && !delta->ptr) return fail(OPENR_SPF_EINVAL, "null delta->ptr");
+  if (delta && delta->cap && (!delta->group || !delta->metric || !delta->nh || !delta->alt))
+    return fail(OPENR_SPF_EINVAL, "null delta->group, metric, nh or alt");
+  const uint32_t need = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
+  if (delta && delta->nh_bytes < need) return fail(OPENR_SPF_EINVAL, "nh_bytes %u < required %u", delta->nh_bytes, need);
+  if ((rc = check_routes_metric(ctx, flags)) != OPENR_SPF_OK) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint32_t nhb = delta ? delta->nh_bytes : need;
+  const uint64_t cap = delta ? delta->cap : 0u;
+  std::vector<uint32_t> rebased, idx;
+  std::vector<uint64_t> ptr;
+  const uint32_t nd = (uint32_t)ctx->devs.size();
+  const uint32_t per = (n_sets + nd - 1) / std::max<uint32_t>(nd, 1);
+  uint64_t solved_total = 0, at = 0;
+  bool over = false;
+  if (delta) delta->ptr[0] = 0;
+  for (uint32_t di = 0; di < nd; ++di) {
+    Device& d = ctx->devs[di];
+    const uint32_t b = std::min(n_sets, di * per), e = std::min(n_sets, b + per), m = e - b;
+    if (!m || !n_sources) continue;
+    const size_t mu = (size_t)m * n_sources, uo = (size_t)b * n_sources;
+    HIP_TRY(hipSetDevice(d.ordinal));
+    WhatifUnits un;
+    if ((rc = upload_whatif_units(d, hu, b, m, &rebased, &un)) != OPENR_SPF_OK) return rc;
+    DevGroups gr;
+    if ((rc = upload_groups(d, g, &gr)) != OPENR_SPF_OK) return rc;
+    HIP_TRY(d.win_src.reserve(n_sources));
+    HIP_TRY(d.wl_ochanged.reserve(mu));
+    HIP_TRY(d.wl_ounprot.reserve(mu));
+    HIP_TRY(d.wl_olost.reserve(mu));
+    HIP_TRY(d.wl_optr.reserve(mu + 1));
+    HIP_TRY(hipMemcpyAsync(d.win_src.p, sources, n_sources * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    // the device's entries land in library buffers sized to the room left in the caller's
+    const uint64_t room = cap > at ? cap - at : 0;
+    if (delta) {
+      HIP_TRY(d.wl_ogroup.reserve(std::max<uint64_t>(room, 1)));
+      HIP_TRY(d.wl_ometric.reserve(std::max<uint64_t>(room, 1)));
+      HIP_TRY(d.wl_onh.reserve(std::max<uint64_t>(room * nhb, 1)));
+      HIP_TRY(d.wl_oalt.reserve(std::max<uint64_t>(room * nhb, 1)));
+    }
+    WlfaOut out;
+    out.changed = d.wl_ochanged.p;
+    out.unprot = unprotected ? d.wl_ounprot.p : nullptr;
+    out.lost = lost_backup ? d.wl_olost.p : nullptr;
+    out.ptr = delta ? reinterpret_cast<uint64_t*>(d.wl_optr.p) : nullptr;
+    out.group = d.wl_ogroup.p;
+    out.metric = reinterpret_cast<uint64_t*>(d.wl_ometric.p);
+    out.nh = d.wl_onh.p;
+    out.alt = d.wl_oalt.p;
+    out.cap = room;
+    out.nhb = nhb;
+    uint64_t total = 0, solved = 0;
+    rc = whatif_lfa_on_device(ctx, d, un, d.win_src.p, n_sources, flags, gr, out, d.stream, &total, &solved);
+    if (rc && rc != OPENR_SPF_E2BIG) return rc;
+    over |= rc == OPENR_SPF_E2BIG;
+    solved_total += solved;
+    HIP_TRY(hipMemcpyAsync(changed + uo, d.wl_ochanged.p, mu * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+    if (unprotected)
+      HIP_TRY(hipMemcpyAsync(unprotected + uo, d.wl_ounprot.p, mu * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+    if (lost_backup)
+      HIP_TRY(hipMemcpyAsync(lost_backup + uo, d.wl_olost.p, mu * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+    const bool fits = delta && !over && total <= room;
+    if (delta) {
+      ptr.resize(mu + 1);
+      HIP_TRY(hipMemcpyAsync(ptr.data(), d.wl_optr.p, (mu + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+    }
+    if (fits && total) {
+      HIP_TRY(hipMemcpyAsync(delta->group + at, d.wl_ogroup.p, total * 4u, hipMemcpyDeviceToHost, d.stream));
+      HIP_TRY(hipMemcpyAsync(delta->metric + at, d.wl_ometric.p, total * 8u, hipMemcpyDeviceToHost, d.stream));
+      HIP_TRY(hipMemcpyAsync(delta->nh + at * nhb, d.wl_onh.p, total * nhb, hipMemcpyDeviceToHost, d.stream));
+      HIP_TRY(hipMemcpyAsync(delta->alt + at * nhb, d.wl_oalt.p, total * nhb, hipMemcpyDeviceToHost, d.stream));
+    }
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    for (size_t u = 0; delta && u < mu; ++u) {
+      delta->ptr[uo + u + 1] = at + ptr[u + 1];
+      const uint32_t c = (uint32_t)(ptr[u + 1] - ptr[u]);
+      if (!fits || c < 2) continue;
+      // each unit's groups ascending (the device keeps the kernel's order)
+      const uint64_t o = at + ptr[u];
+      idx.resize(c);
+      for (uint32_t k = 0; k < c; ++k) idx[k] = k;
+      std::sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return delta->group[o + x] < delta->group[o + y]; });
+      std::vector<uint32_t> tg(c);
+      std::vector<uint64_t> tm(c);
+      std::vector<uint8_t> th((size_t)c * nhb), ta((size_t)c * nhb);
+      for (uint32_t k = 0; k < c; ++k) {
+        tg[k] = delta->group[o + idx[k]];
+        tm[k] = delta->metric[o + idx[k]];
+        std::memcpy(&th[(size_t)k * nhb], delta->nh + (o + idx[k]) * nhb, nhb);
+        std::memcpy(&ta[(size_t)k * nhb], delta->alt + (o + idx[k]) * nhb, nhb);
+      }
+      std::memcpy(delta->group + o, tg.data(), c * 4u);
+      std::memcpy(delta->metric + o, tm.data(), c * 8u);
+      std::memcpy(delta->nh + o * nhb, th.data(), (size_t)c * nhb);
+      std::memcpy(delta->alt + o * nhb, ta.data(), (size_t)c * nhb);
+    }
+    at += total;
+  }
+  ctx->stats.last_batch_ms =
+      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (out_solved) *out_solved = solved_total;
+  if (delta && (over || at > cap))
+    return fail(OPENR_SPF_E2BIG, "%llu entries changed, cap %llu (ptr and the counts are filled, entries are not)",
+                (unsigned long long)at, (unsigned long long)cap);
+  return OPENR_SPF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2187,6 +2523,11 @@ void openr_spf_destroy(openr_spf_ctx* ctx) {
                    d.lf_nalt.p,  d.lf_onbr.p,  d.lf_wptr.p, d.lf_tsum.p,  d.lf_ttome.p,  d.lf_tfrom.p,
                    d.lf_optr.p,  d.lf_oam.p,   d.lf_nh.p,   d.lf_alt.p};
     for (void* p : lfa)
+      if (p) (void)hipFree(p);
+    void* wlfa[] = {d.wl_clos.p,     d.wl_bunprot.p, d.wl_alist.p,  d.wl_acount.p, d.wl_bm.p,
+                    d.wl_ochanged.p, d.wl_ounprot.p, d.wl_olost.p,  d.wl_ogroup.p, d.wl_optr.p,
+                    d.wl_ometric.p,  d.wl_balt.p,    d.wl_onh.p,    d.wl_oalt.p};
+    for (void* p : wlfa)
       if (p) (void)hipFree(p);
     void* sweep[] = {d.base_dist.p, d.base_tight.p, d.wdist.p, d.base_nh.p, d.wnh.p, d.wsrc.p, d.wlink.p,
                      d.wunit.p,     d.wcount.p,     d.wiota.p, d.base_tin.p, d.win_links.p, d.win_src.p, d.wchanged.p, d.wchanged_t.p,
@@ -3088,6 +3429,64 @@ int openr_spf_lfa_routes_device(openr_spf_ctx* ctx, int device_index, const uint
   uint64_t total = 0, solved = 0;
   rc = lfa_on_device(ctx, d, d_sources, n, flags, gr, out, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream,
                      &total, &solved);
+  if (out_total) *out_total = total;
+  if (out_solved) *out_solved = solved;
+  return rc;
+}
+
+int openr_spf_whatif_lfa(openr_spf_ctx* ctx, const uint32_t* set_ptr, const uint32_t* set_links, uint32_t n_sets,
+                         const uint32_t* sources, uint32_t n_sources, uint32_t flags,
+                         const openr_spf_groups_t* groups, uint32_t* changed, uint32_t* unprotected,
+                         uint32_t* lost_backup, openr_spf_whatif_lfa_t* delta, uint64_t* out_solved) {
+  if (n_sets && !set_ptr) return fail(OPENR_SPF_EINVAL, "null set_ptr");
+  return whatif_lfa_host(ctx, host_sets(set_ptr, set_links, n_sets), sources, n_sources, flags, groups, changed,
+                         unprotected, lost_backup, delta, out_solved);
+}
+
+int openr_spf_whatif_lfa_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_set_ptr,
+                                const uint32_t* d_set_links, uint32_t n_sets, uint32_t n_set_links,
+                                const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                                const uint32_t* d_group_ptr, const uint32_t* d_group_nodes, uint32_t n_groups,
+                                uint32_t n_group_nodes, uint32_t* d_changed, uint32_t* d_unprotected,
+                                uint32_t* d_lost_backup, uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric,
+                                uint8_t* d_nh, uint8_t* d_alt, uint64_t cap, uint32_t nh_bytes, void* stream,
+                                uint64_t* out_total, uint64_t* out_solved) {
+  clear_launch_trace();
+  if (out_total) *out_total = 0;
+  if (out_solved) *out_solved = 0;
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (device_index < 0 || device_index >= (int)ctx->devs.size())
+    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+  if ((n_sets && !d_set_ptr) || (n_sources && !d_sources) || (n_sets && n_sources && !d_changed))
+    return fail(OPENR_SPF_EINVAL, "null sets, sources or changed");
+  if ((n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes))
+    return fail(OPENR_SPF_EINVAL, "null group_ptr or group_nodes");
+  if (cap && (!d_ptr || !d_group || !d_metric || !d_nh || !d_alt)) return fail(OPENR_SPF_EINVAL, "null entry buffer");
+  int rc = check_routes_metric(ctx, flags);
+  if (rc) return rc;
+  Device& d = ctx->devs[device_index];
+  HIP_TRY(hipSetDevice(d.ordinal));
+  DevGroups gr;
+  gr.ptr = d_group_ptr;
+  gr.nodes = d_group_nodes;
+  gr.n = n_groups;
+  gr.m = n_group_nodes;
+  WlfaOut out;
+  out.changed = d_changed;
+  out.unprot = d_unprotected;
+  out.lost = d_lost_backup;
+  out.ptr = d_ptr;
+  out.group = d_group;
+  out.metric = d_metric;
+  out.nh = d_nh;
+  out.alt = d_alt;
+  out.cap = cap;
+  out.nhb = nh_bytes;
+  uint64_t total = 0, solved = 0;
+  rc = whatif_lfa_on_device(ctx, d, device_sets(d_set_ptr, d_set_links, n_sets, n_set_links), d_sources, n_sources,
+                            flags, gr, out, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream, &total,
+                            &solved);
   if (out_total) *out_total = total;
   if (out_solved) *out_solved = solved;
   return rc;

@@ -406,6 +406,65 @@ hipError_t launch_lfa_reduce(const LfaPass& p, bool emit, int num_cus, hipStream
 hipError_t launch_lfa_ptr_shift(unsigned long long* ptr, size_t n, unsigned long long carry, int num_cus,
                                 hipStream_t s);
 
+// Post-failure loop-free alternates (spf_wlfa.hip): the LFA entry (metric, nh, alt) of every
+// (failure set i, source j, group k) where it differs from the no-failure entry, from the
+// node deltas of a link-set sweep over sets x rows (rows = the sources, then their up
+// neighbours that are no source: launch_lfa_rows; unit i * n_rows + row). The rule is in that
+// file's header and at openr_spf_whatif_lfa.
+struct WlfaPass {
+  uint32_t V, G, M, n_src, n_rows, n_sets, n_set_links, nb, onb;
+  const uint32_t* set_ptr;
+  const uint32_t* set_links;
+  const uint32_t* sources;
+  const uint2* row2;
+  const uint32_t* adj;
+  const uint32_t* lid;
+  const uint16_t* nbr;
+  const uint32_t* rowidx;
+  const uint32_t* gptr;
+  const uint32_t* gnodes;
+  const unsigned long long* iptr;
+  const uint32_t* inv;
+  const uint32_t* nchanged;           // [n_sets * n_rows] the sweep's changed-node counts
+  const unsigned long long* nptr;     // node delta CSR over the sweep's units
+  const uint32_t* nnode;
+  const unsigned long long* ndist;
+  const uint8_t* nnh;                 // [.][nb]
+  const unsigned long long* bdist;    // base rows [n_rows][V]
+  const uint8_t* bnh;                 // [n_rows][V][nb] (read for the sources only)
+  const uint32_t* trow;               // base neighbour table (launch_lfa_table)
+  const unsigned long long* ttome;
+  const unsigned long long* bmetric;  // base entries [n_src][G]
+  const uint8_t* bmnh;                // [n_src][G][nb]
+  const uint8_t* balt;                // [n_src][G][nb]
+  uint32_t* bunprot;                  // [n_src] base unprotected count (written by the mark launch)
+  uint32_t* alist;                    // [units] affected units, *acount of them
+  uint32_t* acount;
+  uint32_t* changed;                  // [units]
+  uint32_t* unprot;                   // [units], nullable
+  uint32_t* lost;                     // [units], nullable
+  const unsigned long long* optr;     // emit pass: [units + 1]
+  uint32_t* ogroup;
+  unsigned long long* ometric;
+  uint8_t* onh;                       // [.][onb], zero past nb
+  uint8_t* oalt;                      // [.][onb], zero past nb
+  uint32_t hash_slots, hash_shift, cand_cap, bm_lds, slots;  // WlfaLayout (set by the launcher)
+  uint32_t* g_bm;                     // [grid][ceil(G / 32)] when the bitmap is not in LDS
+};
+// Per-workgroup structures and the grid: hash slots (0: lookups scan the delta slices), the
+// candidate list, whether the candidate bitmap is in LDS (else bm_words u32 of global
+// scratch), the neighbour slots staged at a time. No limit changes a result.
+struct WlfaLayout {
+  uint32_t hash_slots = 0, hash_shift = 0, cand_cap = 0, bm_lds = 1, slots = 8, lds_bytes = 0, grid = 1;
+  size_t bm_words = 0;
+};
+WlfaLayout whatif_lfa_layout(uint32_t G, size_t units, int num_cus);
+// bunprot, then per unit changed = 0, lost = 0, unprot = bunprot[j], and the affected list
+hipError_t launch_wlfa_mark(const WlfaPass& p, int num_cus, hipStream_t s);
+// Count pass: changed / unprot / lost of every listed unit. Emit pass: its entries at
+// optr[u] + rank in the pass (any order inside a unit), nothing at or past optr[u + 1].
+hipError_t launch_wlfa(const WlfaPass& p, const WlfaLayout& l, bool emit, hipStream_t s);
+
 // Incremental mirror updates (spf_update.hip).
 // In-place attribute patch of the device mirror: each record overwrites one element of
 // one DevGraph array (structure — rows, columns, link ids — never changes).

@@ -56,6 +56,8 @@ EXPORTS = (
     "openr_spf_whatif_routes_device",
     "openr_spf_lfa_routes",
     "openr_spf_lfa_routes_device",
+    "openr_spf_whatif_lfa",
+    "openr_spf_whatif_lfa_device",
     "openr_spf_ksp2",
     "openr_spf_ksp2_device",
     "openr_spf_host_alloc",
@@ -143,6 +145,18 @@ class LfaEntries(ctypes.Structure):  # openr_spf_lfa_entries_t
     ]
 
 
+class WhatifLfa(ctypes.Structure):  # openr_spf_whatif_lfa_t
+    _fields_ = [
+        ("ptr", ctypes.c_void_p),
+        ("group", ctypes.c_void_p),
+        ("metric", ctypes.c_void_p),
+        ("nh", ctypes.c_void_p),
+        ("alt", ctypes.c_void_p),
+        ("cap", ctypes.c_uint64),
+        ("nh_bytes", ctypes.c_uint32),
+    ]
+
+
 class SpfLimits(ctypes.Structure):
     _fields_ = [("max_nodes", ctypes.c_uint32), ("max_nh_bits", ctypes.c_uint32)]
 
@@ -211,6 +225,11 @@ def load_library():
     l.openr_spf_lfa_routes_device.argtypes = [vp, ctypes.c_int, vp, u32, u32, vp, vp, u32, u32, vp, vp, vp, u32, vp,
                                               vp, vp, vp, ctypes.c_uint64, vp, P(ctypes.c_uint64),
                                               P(ctypes.c_uint64)]
+    l.openr_spf_whatif_lfa.argtypes = [vp, vp, vp, u32, vp, u32, u32, P(SpfGroups), vp, vp, vp, P(WhatifLfa),
+                                       P(ctypes.c_uint64)]
+    l.openr_spf_whatif_lfa_device.argtypes = [vp, ctypes.c_int, vp, vp, u32, u32, vp, u32, u32, vp, vp, u32, u32,
+                                              vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_uint64, u32, vp,
+                                              P(ctypes.c_uint64), P(ctypes.c_uint64)]
     l.openr_spf_ksp2.argtypes = [vp, vp, vp, u32, u32, vp, vp]
     l.openr_spf_ksp2_device.argtypes = [vp, ctypes.c_int, vp, u32, vp, vp, u32, u32, vp, vp, vp]
     l.openr_spf_host_alloc.argtypes = [ctypes.c_size_t, P(vp)]
@@ -629,6 +648,70 @@ class SpfEngine:
             n_groups, n_group_nodes, vp(d_metric), vp(d_nh or None), vp(d_alt or None), nh_bytes or self.nh_bytes,
             vp(d_n_alt or None), vp(d_ptr or None), vp(d_nbr or None), vp(d_alt_metric or None), cap,
             vp(stream or None), ctypes.byref(total), ctypes.byref(solved))
+        if not (allow_overflow and rc == E2BIG):
+            _check(rc)
+        return int(total.value), int(solved.value)
+
+    def whatif_lfa(self, sets: Sequence[Sequence[int]], sources: Sequence[int], groups: Sequence[Sequence[int]],
+                   use_link_metric: bool = True, nh_bytes: Optional[int] = None, cap: Optional[int] = None,
+                   want_counts: bool = True):
+        """Post-failure loop-free alternates (openr_spf_whatif_lfa): (changed[n_sets, n_sources]
+        u32, ptr[n_units + 1] u64, group u32, metric u64, nh[entries, nh_bytes] u8, alt[entries,
+        nh_bytes] u8, unprotected[n_sets, n_sources] u32 | None, lost_backup[...] u32 | None, SPFs
+        run). Unit u = i * n_sources + j owns entries [ptr[u], ptr[u + 1]): the groups whose LFA
+        RIB entry (metric, nh or alt) the failure of sets[i] changes at sources[j], group ids
+        ascending, with the new entry. unprotected counts the groups left live with a single next
+        hop in nh | alt, lost_backup those that had two or more before (want_counts False: both
+        None). cap None: sized from a counts-only call."""
+        n = len(sets)
+        sp, sl = _ignore_arrays(sets, n)
+        gp, gn = _ignore_arrays(groups, len(groups))
+        gs = SpfGroups(len(groups), _p(gp), _p(gn))
+        src = np.ascontiguousarray(sources, dtype=np.uint32)
+        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
+        unprot = np.zeros((n, src.shape[0]), dtype=np.uint32) if want_counts else None
+        lost = np.zeros((n, src.shape[0]), dtype=np.uint32) if want_counts else None
+        solved = ctypes.c_uint64()
+
+        def call(d):
+            return self._lib.openr_spf_whatif_lfa(self._ctx, _p(sp), _p(sl), n, _p(src), src.shape[0], flags,
+                                                  ctypes.byref(gs), _p(changed), _p(unprot), _p(lost), d,
+                                                  ctypes.byref(solved))
+
+        if cap is None:
+            _check(call(None))
+            cap = int(changed.sum(dtype=np.uint64))
+        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
+        group = np.zeros(max(cap, 1), dtype=np.uint32)
+        metric = np.zeros(max(cap, 1), dtype=np.uint64)
+        nh = np.zeros((max(cap, 1), max(nb, 1)), dtype=np.uint8)
+        alt = np.zeros((max(cap, 1), max(nb, 1)), dtype=np.uint8)
+        d = WhatifLfa(_p(ptr), _p(group), _p(metric), _p(nh), _p(alt), cap, nb)
+        _check(call(ctypes.byref(d)))
+        k = int(ptr[-1])
+        return changed, ptr, group[:k], metric[:k], nh[:k], alt[:k], unprot, lost, int(solved.value)
+
+    def whatif_lfa_device(self, d_set_ptr: int, d_set_links: int, n_sets: int, n_set_links: int, d_sources: int,
+                          n_sources: int, d_group_ptr: int, d_group_nodes: int, n_groups: int, n_group_nodes: int,
+                          d_changed: int, d_unprotected: int = 0, d_lost_backup: int = 0, d_ptr: int = 0,
+                          d_group: int = 0, d_metric: int = 0, d_nh: int = 0, d_alt: int = 0, cap: int = 0,
+                          nh_bytes: int = 0, use_link_metric: bool = True, stream: int = 0, device_index: int = 0,
+                          allow_overflow: bool = False) -> Tuple[int, int]:
+        """Device-pointer form (openr_spf_whatif_lfa_device): (total entries, SPFs run). d_ptr 0:
+        counts only; else d_ptr [n_units + 1] u64 CSR, unit u's entries in the kernel's order.
+        Synchronizes ``stream``."""
+        vp = ctypes.c_void_p
+        total = ctypes.c_uint64()
+        solved = ctypes.c_uint64()
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        rc = self._lib.openr_spf_whatif_lfa_device(
+            self._ctx, device_index, vp(d_set_ptr or None), vp(d_set_links or None), n_sets, n_set_links,
+            vp(d_sources or None), n_sources, flags, vp(d_group_ptr or None), vp(d_group_nodes or None), n_groups,
+            n_group_nodes, vp(d_changed or None), vp(d_unprotected or None), vp(d_lost_backup or None),
+            vp(d_ptr or None), vp(d_group or None), vp(d_metric or None), vp(d_nh or None), vp(d_alt or None), cap,
+            nh_bytes or self.nh_bytes, vp(stream or None), ctypes.byref(total), ctypes.byref(solved))
         if not (allow_overflow and rc == E2BIG):
             _check(rc)
         return int(total.value), int(solved.value)
