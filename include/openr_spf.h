@@ -542,6 +542,71 @@ int openr_spf_whatif_lfa_device(openr_spf_ctx* ctx, int device_index, const uint
                                 uint8_t* d_nh, uint8_t* d_alt, uint64_t cap, uint32_t nh_bytes, void* stream,
                                 uint64_t* out_total, uint64_t* out_solved);
 
+/* Drain what-if sweep: what moves when an operator drains routers or links before
+   maintenance. A drain event i is a set of nodes N_i, which get the overload bit, and
+   optionally a set of links K_i, which are overloaded links (Link::isUp() is false: unusable
+   in both directions). Unit (i, j) is runSpf(sources[j], useLinkMetric, K_i) on the graph in
+   which every node of N_i has node_overloaded = 1, compared with the no-event SPF of
+   sources[j]. A drained node is not a failed node: it stays reachable and keeps its own
+   prefixes, but carries no transit traffic ("reached, never expanded", LinkState.cpp:831-838).
+     - a drained node that is the unit's source still expands;
+     - a node that is overloaded already changes nothing;
+     - a node or link listed twice counts once; an empty event changes nothing;
+     - next-hop bit positions are those of the unmodified graph (openr_spf_neighbor_map).
+   changed [n_events][n_sources] = nodes whose distance or next-hop bytes differ (a node that
+   becomes unreachable counts). delta (nullable: counts only) is the CSR of
+   openr_spf_whatif_sets_delta over units u = i * n_sources + j: node ids ascending, dist
+   UINT64_MAX = unreachable; OPENR_SPF_E2BIG means sum(changed) > cap and nothing else.
+   *out_solved (nullable) = base solves + affected units (units with a removed edge on a
+   shortest path of the source); it is added to stats.spf_runs. Events are split in
+   contiguous blocks across the context's devices.
+   Errors: OPENR_SPF_EINVAL for a null or non-ascending node_ptr / link_ptr, a node >= V, a
+   link >= L, or n_events * n_sources > 2^32 - 1; OPENR_SPF_ENOTSUP when the base SPF needs
+   the exact-order kernel (zero or wrapped metrics under link metric, next-hop sets wider
+   than 256 bits, OPENR_SPF_FORCE_EXACT; the hop-count form of such a graph is served);
+   OPENR_SPF_E2BIG when a unit's state does not fit LDS. Not covered: loop-free alternates
+   under a drain, metric-increase (soft-drain) events. */
+typedef struct {
+  uint32_t n_events;
+  const uint32_t* node_ptr;  /* [n_events + 1] */
+  const uint32_t* nodes;     /* drained node ids */
+  const uint32_t* link_ptr;  /* nullable: no links in any event; else [n_events + 1] */
+  const uint32_t* links;     /* drained (unusable) link ids */
+} openr_spf_drain_events_t;
+int openr_spf_whatif_drain(openr_spf_ctx* ctx, const openr_spf_drain_events_t* events, const uint32_t* sources,
+                           uint32_t n_sources, uint32_t flags, uint32_t* changed, openr_spf_whatif_delta_t* delta,
+                           uint64_t* out_solved);
+
+/* Device-buffer form (every buffer device memory), conventions of
+   openr_spf_whatif_sets_delta_device: d_nodes holds n_nodes entries and d_links n_links
+   (d_link_ptr NULL: no links); every slice is clamped to them and ids out of range are
+   skipped, nothing is read out of bounds. d_changed [n_events][n_sources], d_ptr
+   [n_units + 1], entries of a unit in the order the kernel found them (not sorted). cap 0:
+   counts and ptr only; when the total exceeds cap the entries are not written and the call
+   returns OPENR_SPF_E2BIG. *out_total (host, nullable) = sum(changed). Synchronizes `stream`. */
+int openr_spf_whatif_drain_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
+                                  const uint32_t* d_nodes, const uint32_t* d_link_ptr, const uint32_t* d_links,
+                                  uint32_t n_events, uint32_t n_nodes, uint32_t n_links, const uint32_t* d_sources,
+                                  uint32_t n_sources, uint32_t flags, uint32_t* d_changed, uint64_t* d_ptr,
+                                  uint32_t* d_node, uint64_t* d_dist, uint8_t* d_nh, uint64_t cap, uint32_t nh_bytes,
+                                  void* stream, uint64_t* out_total, uint64_t* out_solved);
+
+/* The same sweep resolved to routes over a group table: outputs, route rule and errors of
+   openr_spf_whatif_routes[_device], units and errors of openr_spf_whatif_drain[_device]. The
+   loopback route of a drained node keeps a finite metric wherever the base SPF reached it. */
+int openr_spf_whatif_drain_routes(openr_spf_ctx* ctx, const openr_spf_drain_events_t* events, const uint32_t* sources,
+                                  uint32_t n_sources, uint32_t flags, const openr_spf_groups_t* groups,
+                                  uint32_t* changed_routes, openr_spf_whatif_routes_t* delta, uint64_t* out_solved);
+int openr_spf_whatif_drain_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
+                                         const uint32_t* d_nodes, const uint32_t* d_link_ptr, const uint32_t* d_links,
+                                         uint32_t n_events, uint32_t n_nodes, uint32_t n_links,
+                                         const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                                         const uint32_t* d_group_ptr, const uint32_t* d_group_nodes,
+                                         uint32_t n_groups, uint32_t n_group_nodes, uint32_t* d_changed_routes,
+                                         uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
+                                         uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes, void* stream,
+                                         uint64_t* out_total, uint64_t* out_solved);
+
 /* LinkState::getKthPaths(src[i], dst[i], 1) and (.., 2) (LinkState.cpp:762-791, with
    traceOnePath :398-419) for a batch of pairs, traced on the device. Per pair, tok1 /
    tok2 [n_pairs][tok_cap] hold [n_paths, len_0, e.., len_1, e.., ...]: every path as

@@ -90,6 +90,7 @@ struct Device {
   DevBuf<uint32_t> wsrc, wlink, wunit, wcount, wiota, win_links, win_src, wchanged;
   DevBuf<uint32_t> wbeg, wend, win_ptr;  // link-set sweep: each listed unit's slice of the set CSR; host form's set_ptr
   DevBuf<uint32_t> wchanged_t;  // grouped repair: results source-major, transposed into the caller's rows
+  DevBuf<uint32_t> win_nodes, win_lptr;  // drain sweep, host form: the events' nodes and link_ptr (node_ptr: win_ptr)
   DevBuf<uint16_t> base_tin;  // what-if base SPF: tight in-degree rows (rounds plan)
   size_t wiota_n = 0;  // wiota[0, wiota_n) holds 0, 1, 2, ... (kept across calls)
   // KSP2: base rows, chunk rows, per-chunk ignore slots / sources / pointers, status
@@ -1106,17 +1107,101 @@ int whatif_plans(openr_spf_ctx* ctx, uint32_t flags, Plan* base_plan, Plan* ign_
 
 // The failure units of a what-if sweep on one device: n single links (links), or n link
 // sets in CSR form (set_ptr != nullptr: set i = set_links[set_ptr[i], set_ptr[i + 1])).
+// Or n drain events (node_ptr != nullptr: event i overloads nodes[node_ptr[i], node_ptr[i + 1])
+// and takes set_links[set_ptr[i], set_ptr[i + 1]) out of service; set_ptr null: no links).
 struct WhatifUnits {
   const uint32_t* links = nullptr;
   const uint32_t* set_ptr = nullptr;
   const uint32_t* set_links = nullptr;
   uint32_t n_set_links = 0;  // entries of set_links (the filter clamps every slice to them)
   uint32_t n = 0;
+  const uint32_t* node_ptr = nullptr;
+  const uint32_t* nodes = nullptr;
+  uint32_t n_nodes = 0;  // entries of nodes
 };
+
+// Drain sweep on one device (openr_spf_whatif_drain; spf_drain.hip has the unit semantics):
+// base SPF with tight edges -> drain_filter (source-major list of the units with a removed
+// base-tight edge) -> the count read back (one stream sync) -> drain_repair, one workgroup
+// per listed unit on the base rows -> the units that outgrew its slots (a second 4-byte read)
+// through the same kernel with a slot per node. The caller has checked the plan and the LDS
+// sizes (check_drain).
+hipError_t whatif_drain_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, const WhatifUnits& un,
+                                  const uint32_t* d_sources, uint32_t n_src, uint32_t* d_changed, hipStream_t s,
+                                  uint32_t* solved, bool use_link_metric, const WhatifDelta& dl) {
+  *solved = 0;
+  if (!n_src || !un.n) return hipSuccess;
+  const size_t units = (size_t)un.n * n_src;
+  if (units > 0xFFFFFFFFull || base_plan.exact) return hipErrorInvalidValue;
+  hipError_t err;
+#define OPENR_TRY(x)                   \
+  do {                                 \
+    if ((err = (x)) != hipSuccess) return err; \
+  } while (0)
+  bool base_tin = false;
+  OPENR_TRY(whatif_base_solve(ctx, d, base_plan, d_sources, n_src, s, &base_tin));
+  OPENR_TRY(d.wunit.reserve(units));
+  OPENR_TRY(d.wsrc.reserve(units));
+  OPENR_TRY(d.wcount.reserve(3));
+  DrainPass p{};
+  p.n_events = un.n;
+  p.n_nodes = un.n_nodes;
+  p.n_links = un.n_set_links;
+  p.n_src = n_src;
+  p.nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
+  p.unit_cost = use_link_metric ? 0u : 1u;
+  p.node_ptr = un.node_ptr;
+  p.nodes = un.nodes;
+  p.link_ptr = un.set_ptr;
+  p.links = un.set_links;
+  p.sources = d_sources;
+  p.base_dist = d.base_dist.p;
+  p.base_nh = d.base_nh.p;
+  p.base_tight = d.base_tight.p;
+  p.base_tin = base_tin ? d.base_tin.p : nullptr;
+  p.changed = d_changed;
+  p.wunit = d.wunit.p;
+  p.ovf_unit = d.wsrc.p;
+  p.wcount = d.wcount.p;
+  p.ctr = d.work.p + kDrainCtr;
+  p.delta = dl;
+  OPENR_TRY(launch_drain_filter(d.g, p, d.num_cus, s));
+  uint32_t count = 0;
+  OPENR_TRY(hipMemcpyAsync(&count, d.wcount.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  OPENR_TRY(hipStreamSynchronize(s));
+  *solved = count;
+  if (!count) return hipSuccess;
+  OPENR_TRY(launch_drain_repair(d.g, p, count, false, d.num_cus, s));
+  uint32_t over = 0;
+  OPENR_TRY(hipMemcpyAsync(&over, d.wcount.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  OPENR_TRY(hipStreamSynchronize(s));
+  if (over) OPENR_TRY(launch_drain_repair(d.g, p, over, true, d.num_cus, s));
+#undef OPENR_TRY
+  return hipSuccess;
+}
+
+// Plan and capacity checks of the drain calls: the repair reads base_tight rows, which the
+// exact-order kernel's history-dependent pop order does not give a meaning the rule can use.
+int check_drain(const openr_spf_ctx* ctx, uint32_t flags, uint64_t n_events, uint64_t n_sources) {
+  if (n_events * n_sources > 0xFFFFFFFFull) return fail(OPENR_SPF_EINVAL, "more than 2^32 - 1 units");
+  Plan bp;
+  int rc = make_plan(ctx, flags, false, &bp);
+  if (rc) return rc;
+  if (bp.exact)
+    return fail(OPENR_SPF_ENOTSUP, "drain sweep needs a base plan outside the exact-order kernel (usable metrics in "
+                                   "[1, 2^31-1] under link metric, next-hop sets <= 256 bits)");
+  const uint32_t nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
+  if (!drain_lds_bytes(ctx->V, ctx->L, std::min(drain_slots(), ctx->V), nb) ||
+      !drain_lds_bytes(ctx->V, ctx->L, ctx->V, nb))
+    return fail(OPENR_SPF_E2BIG, "a drain unit's state does not fit LDS (V=%u, L=%u)", ctx->V, ctx->L);
+  return OPENR_SPF_OK;
+}
 
 hipError_t whatif_units_on_device(openr_spf_ctx* ctx, Device& d, const Plan& bp, const Plan& ip, const WhatifUnits& un,
                                   const uint32_t* d_sources, uint32_t n_src, uint32_t* d_changed, hipStream_t s,
                                   uint32_t* solved, bool use_link_metric, const WhatifDelta& dl = WhatifDelta{}) {
+  if (un.node_ptr)
+    return whatif_drain_on_device(ctx, d, bp, un, d_sources, n_src, d_changed, s, solved, use_link_metric, dl);
   if (un.set_ptr)
     return whatif_sets_on_device(ctx, d, bp, ip, un.set_ptr, un.set_links, un.n, un.n_set_links, d_sources, n_src, d_changed, s,
                                  solved, use_link_metric, dl);
@@ -1163,6 +1248,7 @@ int whatif_delta_on_device(openr_spf_ctx* ctx, Device& d, const WhatifUnits& un,
   dl.cap = (uint32_t)want;
   dl.nhb = nhb;
   dl.used = d.dl_used.p;
+  if (un.node_ptr && !cap) dl.node = nullptr;  // drain sweep, counts and ptr only: the repair writes no entries
   uint32_t solved = 0;
   HIP_TRY(whatif_units_on_device(ctx, d, bp, ip, un, d_sources, n_src, d_changed, s, &solved,
                                  (flags & OPENR_SPF_USE_LINK_METRIC) != 0, dl));
@@ -1190,10 +1276,18 @@ int check_whatif_host(const openr_spf_ctx* ctx, const WhatifUnits& hu, const uin
                       const uint32_t* changed) {
   if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
   if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if ((hu.n && !hu.links && !hu.set_ptr) || (n_sources && !sources) || (hu.n && n_sources && !changed))
+  if ((hu.n && !hu.links && !hu.set_ptr && !hu.node_ptr) || (n_sources && !sources) || (hu.n && n_sources && !changed))
     return fail(OPENR_SPF_EINVAL, "null links, sources or changed");
   for (uint32_t i = 0; i < n_sources; ++i)
     if (sources[i] >= ctx->V) return fail(OPENR_SPF_EINVAL, "source %u out of range (V=%u)", sources[i], ctx->V);
+  if (hu.node_ptr) {  // drain events: the node CSR here, the link CSR (nullable) below
+    for (uint32_t i = 0; i < hu.n; ++i)
+      if (hu.node_ptr[i + 1] < hu.node_ptr[i]) return fail(OPENR_SPF_EINVAL, "node_ptr does not ascend at event %u", i);
+    if (hu.node_ptr[hu.n] > hu.node_ptr[0] && !hu.nodes) return fail(OPENR_SPF_EINVAL, "null nodes");
+    for (uint32_t k = hu.node_ptr[0]; k < hu.node_ptr[hu.n]; ++k)
+      if (hu.nodes[k] >= ctx->V) return fail(OPENR_SPF_EINVAL, "node %u out of range (V=%u)", hu.nodes[k], ctx->V);
+    if (!hu.set_ptr) return OPENR_SPF_OK;
+  }
   if (!hu.set_ptr) {
     for (uint32_t i = 0; i < hu.n; ++i)
       if (hu.links[i] >= ctx->L)
@@ -1215,6 +1309,35 @@ int upload_whatif_units(Device& d, const WhatifUnits& hu, uint32_t b, uint32_t m
                         WhatifUnits* un) {
   *un = WhatifUnits{};
   un->n = m;
+  if (hu.node_ptr) {  // drain events: node CSR in win_ptr / win_nodes, link CSR in win_lptr / win_links
+    const uint32_t nb0 = hu.node_ptr[b], ne0 = hu.node_ptr[b + m];
+    rebased->resize(m + 1);
+    for (uint32_t i = 0; i <= m; ++i) (*rebased)[i] = hu.node_ptr[b + i] - nb0;
+    HIP_TRY(d.win_ptr.reserve(m + 1));
+    HIP_TRY(d.win_nodes.reserve(std::max<uint32_t>(ne0 - nb0, 1u)));
+    HIP_TRY(hipMemcpyAsync(d.win_ptr.p, rebased->data(), (m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    if (ne0 > nb0)
+      HIP_TRY(hipMemcpyAsync(d.win_nodes.p, hu.nodes + nb0, (ne0 - nb0) * sizeof(uint32_t), hipMemcpyHostToDevice,
+                             d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));  // `rebased` is reused below and for the next device's block
+    un->node_ptr = d.win_ptr.p;
+    un->nodes = d.win_nodes.p;
+    un->n_nodes = ne0 - nb0;
+    if (!hu.set_ptr) return OPENR_SPF_OK;
+    const uint32_t lb = hu.set_ptr[b], le = hu.set_ptr[b + m];
+    for (uint32_t i = 0; i <= m; ++i) (*rebased)[i] = hu.set_ptr[b + i] - lb;
+    HIP_TRY(d.win_lptr.reserve(m + 1));
+    HIP_TRY(d.win_links.reserve(std::max<uint32_t>(le - lb, 1u)));
+    HIP_TRY(hipMemcpyAsync(d.win_lptr.p, rebased->data(), (m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    if (le > lb)
+      HIP_TRY(hipMemcpyAsync(d.win_links.p, hu.set_links + lb, (le - lb) * sizeof(uint32_t), hipMemcpyHostToDevice,
+                             d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    un->set_ptr = d.win_lptr.p;
+    un->set_links = d.win_links.p;
+    un->n_set_links = le - lb;
+    return OPENR_SPF_OK;
+  }
   if (!hu.set_ptr) {
     HIP_TRY(d.win_links.reserve(m));
     HIP_TRY(hipMemcpyAsync(d.win_links.p, hu.links + b, m * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
@@ -1380,7 +1503,7 @@ int whatif_device_form(openr_spf_ctx* ctx, int device_index, const WhatifUnits& 
   if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
   if (device_index < 0 || device_index >= (int)ctx->devs.size())
     return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
-  if ((un.n && !un.links && !un.set_ptr) || (n_sources && !d_sources) || (un.n && n_sources && !d_changed))
+  if ((un.n && !un.links && !un.set_ptr && !un.node_ptr) || (n_sources && !d_sources) || (un.n && n_sources && !d_changed))
     return fail(OPENR_SPF_EINVAL, "null links, sources or changed");
   Plan bp, ip;
   int rc = whatif_plans(ctx, flags, &bp, &ip);
@@ -1407,7 +1530,7 @@ int whatif_delta_device_form(openr_spf_ctx* ctx, int device_index, const WhatifU
   if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
   if (device_index < 0 || device_index >= (int)ctx->devs.size())
     return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
-  if ((un.n && !un.links && !un.set_ptr) || (n_sources && !d_sources) || (un.n && n_sources && !d_changed) || !d_ptr)
+  if ((un.n && !un.links && !un.set_ptr && !un.node_ptr) || (n_sources && !d_sources) || (un.n && n_sources && !d_changed) || !d_ptr)
     return fail(OPENR_SPF_EINVAL, "null links, sources, changed or ptr");
   if (cap && (!d_node || !d_dist || !d_nh)) return fail(OPENR_SPF_EINVAL, "null delta buffer");
   Device& d = ctx->devs[device_index];
@@ -1437,6 +1560,33 @@ WhatifUnits device_sets(const uint32_t* d_set_ptr, const uint32_t* d_set_links, 
   un.n_set_links = n_set_links;
   un.n = n_sets;
   return un;
+}
+
+// Drain events as what-if units (host or device memory; n_nodes / n_links: the device form's
+// slice lengths).
+WhatifUnits drain_units(const uint32_t* node_ptr, const uint32_t* nodes, const uint32_t* link_ptr,
+                        const uint32_t* links, uint32_t n_events, uint32_t n_nodes, uint32_t n_links) {
+  WhatifUnits un;
+  un.node_ptr = n_events ? node_ptr : nullptr;
+  un.nodes = nodes;
+  un.n_nodes = n_nodes;
+  un.set_ptr = n_events ? link_ptr : nullptr;
+  un.set_links = links;
+  un.n_set_links = n_links;
+  un.n = n_events;
+  return un;
+}
+
+int check_drain_events(const openr_spf_ctx* ctx, const openr_spf_drain_events_t* ev) {
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (!ev) return fail(OPENR_SPF_EINVAL, "null events");
+  if (ev->n_events && !ev->node_ptr) return fail(OPENR_SPF_EINVAL, "null node_ptr");
+  return OPENR_SPF_OK;
+}
+
+WhatifUnits host_drain(const openr_spf_drain_events_t* ev) {
+  return drain_units(ev->node_ptr, ev->nodes, ev->link_ptr, ev->links, ev->n_events, 0u, 0u);
 }
 
 // ---- route-level calls (spf_routes.hip) ---------------------------------------------------
@@ -2535,6 +2685,8 @@ void openr_spf_destroy(openr_spf_ctx* ctx) {
                      d.kin_src.p,   d.kin_row.p,    d.kin_dst.p, d.ktok1.p,   d.ktok2.p,   d.kq.p, d.kretry.p};
     for (void* p : sweep)
       if (p) (void)hipFree(p);
+    d.win_nodes.release();
+    d.win_lptr.release();
     d.exscratch.release();
     d.order.release();
     d.precs.release();
@@ -3302,6 +3454,88 @@ int openr_spf_whatif_sets_delta(openr_spf_ctx* ctx, const uint32_t* set_ptr, con
   if (n_sets && !set_ptr) return fail(OPENR_SPF_EINVAL, "null set_ptr");
   return whatif_delta_host(ctx, host_sets(set_ptr, set_links, n_sets), sources, n_sources, flags, changed, delta,
                            out_solved);
+}
+
+int openr_spf_whatif_drain(openr_spf_ctx* ctx, const openr_spf_drain_events_t* events, const uint32_t* sources,
+                           uint32_t n_sources, uint32_t flags, uint32_t* changed, openr_spf_whatif_delta_t* delta,
+                           uint64_t* out_solved) {
+  clear_launch_trace();
+  int rc = check_drain_events(ctx, events);
+  if (rc) return rc;
+  const WhatifUnits hu = host_drain(events);
+  if ((rc = check_whatif_host(ctx, hu, sources, n_sources, changed)) != OPENR_SPF_OK) return rc;
+  if ((rc = check_drain(ctx, flags, events->n_events, n_sources)) != OPENR_SPF_OK) return rc;
+  if (!delta) return whatif_host(ctx, hu, sources, n_sources, flags, changed, out_solved);
+  return whatif_delta_host(ctx, hu, sources, n_sources, flags, changed, delta, out_solved);
+}
+
+int openr_spf_whatif_drain_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
+                                  const uint32_t* d_nodes, const uint32_t* d_link_ptr, const uint32_t* d_links,
+                                  uint32_t n_events, uint32_t n_nodes, uint32_t n_links, const uint32_t* d_sources,
+                                  uint32_t n_sources, uint32_t flags, uint32_t* d_changed, uint64_t* d_ptr,
+                                  uint32_t* d_node, uint64_t* d_dist, uint8_t* d_nh, uint64_t cap, uint32_t nh_bytes,
+                                  void* stream, uint64_t* out_total, uint64_t* out_solved) {
+  clear_launch_trace();
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (n_events && (!d_node_ptr || (n_nodes && !d_nodes) || (d_link_ptr && n_links && !d_links)))
+    return fail(OPENR_SPF_EINVAL, "null node_ptr, nodes or links");
+  int rc = check_drain(ctx, flags, n_events, n_sources);
+  if (rc) return rc;
+  return whatif_delta_device_form(ctx, device_index,
+                                  drain_units(d_node_ptr, d_nodes, d_link_ptr, d_links, n_events, n_nodes, n_links),
+                                  d_sources, n_sources, flags, d_changed, d_ptr, d_node, d_dist, d_nh, cap, nh_bytes,
+                                  stream, out_total, out_solved);
+}
+
+int openr_spf_whatif_drain_routes(openr_spf_ctx* ctx, const openr_spf_drain_events_t* events, const uint32_t* sources,
+                                  uint32_t n_sources, uint32_t flags, const openr_spf_groups_t* groups,
+                                  uint32_t* changed_routes, openr_spf_whatif_routes_t* delta, uint64_t* out_solved) {
+  int rc = check_drain_events(ctx, events);
+  if (rc) return rc;
+  const WhatifUnits hu = host_drain(events);
+  if ((rc = check_whatif_host(ctx, hu, sources, n_sources, changed_routes)) != OPENR_SPF_OK) return rc;
+  if ((rc = check_drain(ctx, flags, events->n_events, n_sources)) != OPENR_SPF_OK) return rc;
+  return whatif_routes_host(ctx, hu, sources, n_sources, flags, groups, changed_routes, delta, out_solved);
+}
+
+int openr_spf_whatif_drain_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
+                                         const uint32_t* d_nodes, const uint32_t* d_link_ptr, const uint32_t* d_links,
+                                         uint32_t n_events, uint32_t n_nodes, uint32_t n_links,
+                                         const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                                         const uint32_t* d_group_ptr, const uint32_t* d_group_nodes,
+                                         uint32_t n_groups, uint32_t n_group_nodes, uint32_t* d_changed_routes,
+                                         uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
+                                         uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes, void* stream,
+                                         uint64_t* out_total, uint64_t* out_solved) {
+  clear_launch_trace();
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (device_index < 0 || device_index >= (int)ctx->devs.size())
+    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+  if ((n_events && (!d_node_ptr || (n_nodes && !d_nodes) || (d_link_ptr && n_links && !d_links))) ||
+      (n_sources && !d_sources) || (n_events && n_sources && !d_changed_routes) || !d_ptr)
+    return fail(OPENR_SPF_EINVAL, "null events, sources, changed_routes or ptr");
+  if ((n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes))
+    return fail(OPENR_SPF_EINVAL, "null group_ptr or group_nodes");
+  if (cap && (!d_group || !d_metric || !d_nh)) return fail(OPENR_SPF_EINVAL, "null route buffer");
+  int rc = check_drain(ctx, flags, n_events, n_sources);
+  if (rc) return rc;
+  Device& d = ctx->devs[device_index];
+  HIP_TRY(hipSetDevice(d.ordinal));
+  DevGroups gr;
+  gr.ptr = d_group_ptr;
+  gr.nodes = d_group_nodes;
+  gr.n = n_groups;
+  gr.m = n_group_nodes;
+  uint64_t total = 0, solved = 0;
+  rc = whatif_routes_on_device(ctx, d, drain_units(d_node_ptr, d_nodes, d_link_ptr, d_links, n_events, n_nodes, n_links),
+                               d_sources, n_sources, flags, gr, d_changed_routes, d_ptr, d_group, d_metric, d_nh,
+                               d_n_best, cap, nh_bytes, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream,
+                               &total, &solved);
+  if (out_total) *out_total = total;
+  if (out_solved) *out_solved = solved;
+  return rc;
 }
 
 int openr_spf_routes(openr_spf_ctx* ctx, const uint32_t* sources, uint32_t n, uint32_t flags,

@@ -465,6 +465,45 @@ hipError_t launch_wlfa_mark(const WlfaPass& p, int num_cus, hipStream_t s);
 // optr[u] + rank in the pass (any order inside a unit), nothing at or past optr[u + 1].
 hipError_t launch_wlfa(const WlfaPass& p, const WlfaLayout& l, bool emit, hipStream_t s);
 
+// Drain what-if sweep (spf_drain.hip): unit u = i * n_src + j overloads the nodes of event i
+// (nodes[node_ptr[i], node_ptr[i + 1])) and takes its links (links[link_ptr[i], ..), null
+// link_ptr: none) out of service for sources[j]; the rule is in that file's header and at
+// openr_spf_whatif_drain. Slices are clamped to n_nodes / n_links entries and ids out of
+// range are skipped (a malformed device CSR reads nothing past the arrays).
+struct DrainPass {
+  uint32_t n_events, n_nodes, n_links, n_src, nb, unit_cost;
+  const uint32_t* node_ptr;
+  const uint32_t* nodes;
+  const uint32_t* link_ptr;
+  const uint32_t* links;
+  const uint32_t* sources;
+  const uint64_t* base_dist;   // base rows [n_src][V] (whatif_base_solve)
+  const uint8_t* base_nh;      // [n_src][V][nb]
+  const uint64_t* base_tight;  // [n_src][ceil(E / 64)]
+  const uint16_t* base_tin;    // nullable [n_src][V] tight in-degrees (rounds plan)
+  uint32_t* changed;           // [units]
+  uint32_t* wunit;             // [units] affected units
+  uint32_t* ovf_unit;          // [units] units that outgrew the narrow launch's slots
+  uint32_t* wcount;            // [2] affected units, overflowed units
+  uint32_t* ctr;               // 2 work counters (zero at rest)
+  WhatifDelta delta;           // node == null: counts only
+};
+constexpr uint32_t kDrainCtr = kExactCtr + 2;
+constexpr uint32_t kDrainSlots = 128;      // dirty-node slots of the narrow launch (OPENR_SPF_DRAIN_SLOTS)
+constexpr uint32_t kDrainBlock = 64;       // threads per unit, narrow launch
+constexpr uint32_t kDrainBlockWide = 256;  // ... and the re-run with a slot per node
+uint32_t drain_slots();
+// LDS of a unit with S slots; 0 when it does not fit kMaxLds (or S outgrows the u16 index)
+uint32_t drain_lds_bytes(uint32_t V, uint32_t L, uint32_t S, uint32_t nb);
+// changed[u] = 0 for every unit; the units with a removed base-tight edge are appended
+// source-major to wunit, wcount[0] of them; wcount[1] = 0.
+hipError_t launch_drain_filter(const DevGraph& g, const DrainPass& p, int num_cus, hipStream_t s);
+// Repairs wunit[0, count): changed[] and the delta of every listed unit; units past the
+// slots are appended to ovf_unit (wcount[1]). rerun: repairs ovf_unit[0, count) with a slot
+// per node instead (nothing overflows).
+hipError_t launch_drain_repair(const DevGraph& g, const DrainPass& p, uint32_t count, bool rerun, int num_cus,
+                               hipStream_t s);
+
 // Incremental mirror updates (spf_update.hip).
 // In-place attribute patch of the device mirror: each record overwrites one element of
 // one DevGraph array (structure — rows, columns, link ids — never changes).

@@ -58,6 +58,10 @@ EXPORTS = (
     "openr_spf_lfa_routes_device",
     "openr_spf_whatif_lfa",
     "openr_spf_whatif_lfa_device",
+    "openr_spf_whatif_drain",
+    "openr_spf_whatif_drain_device",
+    "openr_spf_whatif_drain_routes",
+    "openr_spf_whatif_drain_routes_device",
     "openr_spf_ksp2",
     "openr_spf_ksp2_device",
     "openr_spf_host_alloc",
@@ -157,6 +161,16 @@ class WhatifLfa(ctypes.Structure):  # openr_spf_whatif_lfa_t
     ]
 
 
+class DrainEvents(ctypes.Structure):  # openr_spf_drain_events_t
+    _fields_ = [
+        ("n_events", ctypes.c_uint32),
+        ("node_ptr", ctypes.c_void_p),
+        ("nodes", ctypes.c_void_p),
+        ("link_ptr", ctypes.c_void_p),
+        ("links", ctypes.c_void_p),
+    ]
+
+
 class SpfLimits(ctypes.Structure):
     _fields_ = [("max_nodes", ctypes.c_uint32), ("max_nh_bits", ctypes.c_uint32)]
 
@@ -230,6 +244,15 @@ def load_library():
     l.openr_spf_whatif_lfa_device.argtypes = [vp, ctypes.c_int, vp, vp, u32, u32, vp, u32, u32, vp, vp, u32, u32,
                                               vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_uint64, u32, vp,
                                               P(ctypes.c_uint64), P(ctypes.c_uint64)]
+    l.openr_spf_whatif_drain.argtypes = [vp, P(DrainEvents), vp, u32, u32, vp, P(WhatifDelta), P(ctypes.c_uint64)]
+    l.openr_spf_whatif_drain_device.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, u32, u32, u32, vp, u32, u32, vp, vp,
+                                                vp, vp, vp, ctypes.c_uint64, u32, vp, P(ctypes.c_uint64),
+                                                P(ctypes.c_uint64)]
+    l.openr_spf_whatif_drain_routes.argtypes = [vp, P(DrainEvents), vp, u32, u32, P(SpfGroups), vp, P(WhatifRoutes),
+                                                P(ctypes.c_uint64)]
+    l.openr_spf_whatif_drain_routes_device.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, u32, u32, u32, vp, u32, u32,
+                                                       vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, ctypes.c_uint64,
+                                                       u32, vp, P(ctypes.c_uint64), P(ctypes.c_uint64)]
     l.openr_spf_ksp2.argtypes = [vp, vp, vp, u32, u32, vp, vp]
     l.openr_spf_ksp2_device.argtypes = [vp, ctypes.c_int, vp, u32, vp, vp, u32, u32, vp, vp, vp]
     l.openr_spf_host_alloc.argtypes = [ctypes.c_size_t, P(vp)]
@@ -712,6 +735,121 @@ class SpfEngine:
             n_group_nodes, vp(d_changed or None), vp(d_unprotected or None), vp(d_lost_backup or None),
             vp(d_ptr or None), vp(d_group or None), vp(d_metric or None), vp(d_nh or None), vp(d_alt or None), cap,
             nh_bytes or self.nh_bytes, vp(stream or None), ctypes.byref(total), ctypes.byref(solved))
+        if not (allow_overflow and rc == E2BIG):
+            _check(rc)
+        return int(total.value), int(solved.value)
+
+    @staticmethod
+    def _drain_events(node_sets: Sequence[Sequence[int]], link_sets: Optional[Sequence[Sequence[int]]]):
+        """(DrainEvents, the arrays it points into) of per-event node and link lists."""
+        n = len(node_sets)
+        if link_sets is not None and len(link_sets) != n:
+            raise ValueError("node_sets and link_sets differ in length")
+        np_, nn = _ignore_arrays(node_sets, n)
+        lp, ll = _ignore_arrays(link_sets, n) if link_sets is not None else (None, None)
+        return DrainEvents(n, _p(np_), _p(nn), _p(lp), _p(ll)), (np_, nn, lp, ll)
+
+    def whatif_drain(self, node_sets: Sequence[Sequence[int]], sources: Sequence[int],
+                     link_sets: Optional[Sequence[Sequence[int]]] = None, use_link_metric: bool = True,
+                     want_delta: bool = True, cap: Optional[int] = None, nh_bytes: Optional[int] = None):
+        """Drain sweep (openr_spf_whatif_drain): event i overloads the nodes of node_sets[i] and
+        takes the links of link_sets[i] out of service; unit u = i * n_sources + j. Returns the
+        shape of whatif_sets_delta: (changed[n_events, n_sources] u32, ptr, node, dist, nh,
+        solved), or (changed, solved) with want_delta=False. cap None: sized from a count-only
+        pass."""
+        ev, keep = self._drain_events(node_sets, link_sets)
+        n = len(node_sets)
+        src = np.ascontiguousarray(sources, dtype=np.uint32)
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
+        solved = ctypes.c_uint64()
+        if not want_delta or cap is None:
+            _check(self._lib.openr_spf_whatif_drain(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
+                                                    _p(changed), None, ctypes.byref(solved)))
+            if not want_delta:
+                return changed, int(solved.value)
+            cap = int(changed.sum(dtype=np.uint64))
+        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
+        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
+        node = np.zeros(max(cap, 1), dtype=np.uint32)
+        dist = np.zeros(max(cap, 1), dtype=np.uint64)
+        nh = np.zeros((max(cap, 1), nb), dtype=np.uint8)
+        d = WhatifDelta(_p(ptr), _p(node), _p(dist), _p(nh), cap, nb)
+        _check(self._lib.openr_spf_whatif_drain(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
+                                                _p(changed), ctypes.byref(d), ctypes.byref(solved)))
+        del keep
+        k = int(ptr[-1])
+        return changed, ptr, node[:k], dist[:k], nh[:k], int(solved.value)
+
+    def whatif_drain_device(self, d_node_ptr: int, d_nodes: int, d_link_ptr: int, d_links: int, n_events: int,
+                            n_nodes: int, n_links: int, d_sources: int, n_sources: int, d_changed: int, d_ptr: int,
+                            d_node: int, d_dist: int, d_nh: int, cap: int, nh_bytes: int,
+                            use_link_metric: bool = True, stream: int = 0, device_index: int = 0,
+                            allow_overflow: bool = False) -> Tuple[int, int]:
+        """Device-pointer form: (total entries, solved). d_link_ptr 0: no links. d_ptr
+        [n_units + 1] u64 CSR; unit u's entries are [ptr[u], ptr[u + 1]) in the kernel's order."""
+        vp = ctypes.c_void_p
+        total = ctypes.c_uint64()
+        solved = ctypes.c_uint64()
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        rc = self._lib.openr_spf_whatif_drain_device(
+            self._ctx, device_index, vp(d_node_ptr or None), vp(d_nodes or None), vp(d_link_ptr or None),
+            vp(d_links or None), n_events, n_nodes, n_links, vp(d_sources), n_sources, flags, vp(d_changed), vp(d_ptr),
+            vp(d_node or None), vp(d_dist or None), vp(d_nh or None), cap, nh_bytes, vp(stream or None),
+            ctypes.byref(total), ctypes.byref(solved))
+        if not (allow_overflow and rc == E2BIG):
+            _check(rc)
+        return int(total.value), int(solved.value)
+
+    def whatif_drain_routes(self, node_sets: Sequence[Sequence[int]], sources: Sequence[int],
+                            groups: Sequence[Sequence[int]], link_sets: Optional[Sequence[Sequence[int]]] = None,
+                            use_link_metric: bool = True, cap: Optional[int] = None,
+                            nh_bytes: Optional[int] = None):
+        """The drain sweep resolved to routes (openr_spf_whatif_drain_routes): the return shape
+        of whatif_routes. cap None: sized from a count-only pass."""
+        ev, keep = self._drain_events(node_sets, link_sets)
+        n = len(node_sets)
+        gp, gn = _ignore_arrays(groups, len(groups))
+        gs = SpfGroups(len(groups), _p(gp), _p(gn))
+        src = np.ascontiguousarray(sources, dtype=np.uint32)
+        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
+        solved = ctypes.c_uint64()
+        if cap is None:
+            _check(self._lib.openr_spf_whatif_drain_routes(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
+                                                           ctypes.byref(gs), _p(changed), None, ctypes.byref(solved)))
+            cap = int(changed.sum(dtype=np.uint64))
+        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
+        group = np.zeros(max(cap, 1), dtype=np.uint32)
+        metric = np.zeros(max(cap, 1), dtype=np.uint64)
+        nh = np.zeros((max(cap, 1), nb), dtype=np.uint8)
+        n_best = np.zeros(max(cap, 1), dtype=np.uint32)
+        d = WhatifRoutes(_p(ptr), _p(group), _p(metric), _p(nh), _p(n_best), cap, nb)
+        _check(self._lib.openr_spf_whatif_drain_routes(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
+                                                       ctypes.byref(gs), _p(changed), ctypes.byref(d),
+                                                       ctypes.byref(solved)))
+        del keep
+        k = int(ptr[-1])
+        return changed, ptr, group[:k], metric[:k], nh[:k], n_best[:k], int(solved.value)
+
+    def whatif_drain_routes_device(self, d_node_ptr: int, d_nodes: int, d_link_ptr: int, d_links: int, n_events: int,
+                                   n_nodes: int, n_links: int, d_sources: int, n_sources: int, d_group_ptr: int,
+                                   d_group_nodes: int, n_groups: int, n_group_nodes: int, d_changed: int, d_ptr: int,
+                                   d_group: int, d_metric: int, d_nh: int, d_n_best: int, cap: int, nh_bytes: int,
+                                   use_link_metric: bool = True, stream: int = 0, device_index: int = 0,
+                                   allow_overflow: bool = False) -> Tuple[int, int]:
+        """Device-pointer form: (total entries, solved); outputs as whatif_routes_device."""
+        vp = ctypes.c_void_p
+        total = ctypes.c_uint64()
+        solved = ctypes.c_uint64()
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        rc = self._lib.openr_spf_whatif_drain_routes_device(
+            self._ctx, device_index, vp(d_node_ptr or None), vp(d_nodes or None), vp(d_link_ptr or None),
+            vp(d_links or None), n_events, n_nodes, n_links, vp(d_sources), n_sources, flags,
+            vp(d_group_ptr or None), vp(d_group_nodes or None), n_groups, n_group_nodes, vp(d_changed), vp(d_ptr),
+            vp(d_group or None), vp(d_metric or None), vp(d_nh or None), vp(d_n_best or None), cap, nh_bytes,
+            vp(stream or None), ctypes.byref(total), ctypes.byref(solved))
         if not (allow_overflow and rc == E2BIG):
             _check(rc)
         return int(total.value), int(solved.value)

@@ -490,6 +490,22 @@ def srlg_sets(g: CsrGraph, groups: Iterable[Iterable[int]]) -> List[List[int]]:
     return out
 
 
+def drain_events(g: CsrGraph, node_sets: Iterable[Iterable[int]],
+                 link_sets: Optional[Iterable[Iterable[int]]] = None):
+    """Drain events for ``SpfEngine.whatif_drain`` / ``whatif_drain_routes``: per event the
+    nodes that get the overload bit and (optionally) the links taken out of service, every
+    set validated (node ids in [0, num_nodes), link ids in [0, num_links)), de-duplicated and
+    sorted. Returns (node_sets, link_sets); link_sets is None when none were given, else it
+    must have one entry per event."""
+    nodes = prefix_groups(g, node_sets)
+    if link_sets is None:
+        return nodes, None
+    links = srlg_sets(g, link_sets)
+    if len(links) != len(nodes):
+        raise ValueError(f"{len(nodes)} node sets but {len(links)} link sets")
+    return nodes, links
+
+
 def prefix_groups(g: CsrGraph, groups: Iterable[Iterable[int]]) -> List[List[int]]:
     """Caller-given prefix groups (the advertisers of each prefix) as a group table for
     ``SpfEngine.routes`` / ``whatif_routes``: every group validated (node ids in
