@@ -565,7 +565,7 @@ int openr_spf_whatif_lfa_device(openr_spf_ctx* ctx, int device_index, const uint
    the exact-order kernel (zero or wrapped metrics under link metric, next-hop sets wider
    than 256 bits, OPENR_SPF_FORCE_EXACT; the hop-count form of such a graph is served);
    OPENR_SPF_E2BIG when a unit's state does not fit LDS. Not covered: loop-free alternates
-   under a drain, metric-increase (soft-drain) events. */
+   under a drain. Metric raises (soft drains) are openr_spf_whatif_metric below. */
 typedef struct {
   uint32_t n_events;
   const uint32_t* node_ptr;  /* [n_events + 1] */
@@ -606,6 +606,73 @@ int openr_spf_whatif_drain_routes_device(openr_spf_ctx* ctx, int device_index, c
                                          uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
                                          uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes, void* stream,
                                          uint64_t* out_total, uint64_t* out_solved);
+
+/* Metric what-if sweep: what moves when an operator soft-drains a router or a few links by
+   raising metrics before maintenance. Traffic is pushed away, but the node stays a transit
+   of last resort. A metric event i is a list of directed CSR edges (the edge ids of
+   openr_spf_patch_graph) with a new metric each. Unit (i, j) is runSpf(sources[j], true) on
+   the graph in which those edges carry the new metrics, compared with the no-event SPF of
+   sources[j]. Only raises are served: a new metric below the current one is refused.
+     - an entry whose new metric equals the current one changes nothing;
+     - an entry on a down edge changes nothing;
+     - an entry on a row of an overloaded node changes nothing, unless that node is the
+       unit's source (it alone expands such a row);
+     - inside an event the edge ids are strictly ascending; an empty event changes nothing;
+     - next-hop bit positions are those of the unmodified graph (openr_spf_neighbor_map).
+   changed [n_events][n_sources] = nodes whose distance or next-hop bytes differ. A raise
+   disconnects nothing: no node becomes unreachable and no distance shrinks. delta (nullable:
+   counts only) is the CSR of openr_spf_whatif_sets_delta over units u = i * n_sources + j:
+   node ids ascending; OPENR_SPF_E2BIG means sum(changed) > cap and nothing else.
+   *out_solved (nullable) = base solves + affected units (units with a really raised edge on
+   a shortest path of the source); it is added to stats.spf_runs. Events are split in
+   contiguous blocks across the context's devices.
+   Without OPENR_SPF_USE_LINK_METRIC the call is served and launches no kernel: metrics do
+   not enter runSpf(src, false), so every count is 0, ptr is all zero and *out_solved = 0.
+   Errors: OPENR_SPF_EINVAL for a null or non-ascending edge_ptr, an edge >= E, an event
+   slice that is not strictly ascending, a metric below the current one or above 2^31 - 1,
+   or n_events * n_sources > 2^32 - 1; OPENR_SPF_ENOTSUP when the base SPF needs the
+   exact-order kernel (as openr_spf_whatif_drain); OPENR_SPF_E2BIG when a unit's state does
+   not fit LDS. Not covered: metric decreases, events that mix raises with overload bits or
+   link-down sets, loop-free alternates under a metric event. */
+typedef struct {
+  uint32_t n_events;
+  const uint32_t* edge_ptr;  /* [n_events + 1] */
+  const uint32_t* edges;     /* directed CSR edge ids, strictly ascending inside an event */
+  const uint32_t* metrics;   /* the new metric of edges[k] */
+} openr_spf_metric_events_t;
+int openr_spf_whatif_metric(openr_spf_ctx* ctx, const openr_spf_metric_events_t* events, const uint32_t* sources,
+                            uint32_t n_sources, uint32_t flags, uint32_t* changed, openr_spf_whatif_delta_t* delta,
+                            uint64_t* out_solved);
+
+/* Device-buffer form (every buffer device memory), conventions of openr_spf_whatif_drain_device:
+   d_edges and d_metrics hold n_edges entries. Nothing is validated: every slice is clamped
+   to n_edges; an entry with an id >= E, or with a metric <= the current one or > 2^31 - 1,
+   is skipped. For a slice that does not ascend, which of its entries take effect is
+   unspecified; nothing is read out of bounds and every loop terminates. Cap, OPENR_SPF_E2BIG,
+   *out_total and the order of a unit's entries are those of openr_spf_whatif_drain_device.
+   Synchronizes `stream`. */
+int openr_spf_whatif_metric_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_edge_ptr,
+                                   const uint32_t* d_edges, const uint32_t* d_metrics, uint32_t n_events,
+                                   uint32_t n_edges, const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                                   uint32_t* d_changed, uint64_t* d_ptr, uint32_t* d_node, uint64_t* d_dist,
+                                   uint8_t* d_nh, uint64_t cap, uint32_t nh_bytes, void* stream, uint64_t* out_total,
+                                   uint64_t* out_solved);
+
+/* The same sweep resolved to routes over a group table: outputs, route rule and errors of
+   openr_spf_whatif_routes[_device], units and errors of openr_spf_whatif_metric[_device]. No
+   route turns unreachable under a metric event. */
+int openr_spf_whatif_metric_routes(openr_spf_ctx* ctx, const openr_spf_metric_events_t* events,
+                                   const uint32_t* sources, uint32_t n_sources, uint32_t flags,
+                                   const openr_spf_groups_t* groups, uint32_t* changed_routes,
+                                   openr_spf_whatif_routes_t* delta, uint64_t* out_solved);
+int openr_spf_whatif_metric_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_edge_ptr,
+                                          const uint32_t* d_edges, const uint32_t* d_metrics, uint32_t n_events,
+                                          uint32_t n_edges, const uint32_t* d_sources, uint32_t n_sources,
+                                          uint32_t flags, const uint32_t* d_group_ptr, const uint32_t* d_group_nodes,
+                                          uint32_t n_groups, uint32_t n_group_nodes, uint32_t* d_changed_routes,
+                                          uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
+                                          uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes, void* stream,
+                                          uint64_t* out_total, uint64_t* out_solved);
 
 /* LinkState::getKthPaths(src[i], dst[i], 1) and (.., 2) (LinkState.cpp:762-791, with
    traceOnePath :398-419) for a batch of pairs, traced on the device. Per pair, tok1 /

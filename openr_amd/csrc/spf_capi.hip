@@ -81,7 +81,7 @@ struct Device {
   // small multi-class batches: the classes run concurrently, one stream each (forked from
   // and joined back into the caller's stream), each with its own re-run list
   DevBuf<uint32_t> slicetmp;  // code-family sliced class: [n][nsl][V] next-hop chunks
-  DevBuf<uint32_t> work;  // dynamic-scheduling counters (kWorkSlots)
+  DevBuf<uint32_t> work;  // dynamic-scheduling counters (kWorkWords)
   DevBuf<uint32_t> status;  // sticky OPENR_SPF_STATUS_* bits of device-form calls
   DevBuf<uint32_t> perm, part;  // source-class partition of a batch
   // what-if sweep: base SPF rows, the affected-unit work list, chunk result rows
@@ -91,6 +91,7 @@ struct Device {
   DevBuf<uint32_t> wbeg, wend, win_ptr;  // link-set sweep: each listed unit's slice of the set CSR; host form's set_ptr
   DevBuf<uint32_t> wchanged_t;  // grouped repair: results source-major, transposed into the caller's rows
   DevBuf<uint32_t> win_nodes, win_lptr;  // drain sweep, host form: the events' nodes and link_ptr (node_ptr: win_ptr)
+  DevBuf<uint32_t> win_edges, win_metrics;  // metric sweep, host form: the events' edges and new metrics (edge_ptr: win_ptr)
   DevBuf<uint16_t> base_tin;  // what-if base SPF: tight in-degree rows (rounds plan)
   size_t wiota_n = 0;  // wiota[0, wiota_n) holds 0, 1, 2, ... (kept across calls)
   // KSP2: base rows, chunk rows, per-chunk ignore slots / sources / pointers, status
@@ -145,8 +146,8 @@ struct Device {
 // Launch counters live zeroed: each kernel's last workgroup resets what it used.
 hipError_t reserve_counters(Device& d) {
   if (d.work.p) return hipSuccess;
-  hipError_t e = d.work.reserve(kWorkSlots);
-  if (e == hipSuccess) e = hipMemset(d.work.p, 0, kWorkSlots * sizeof(uint32_t));
+  hipError_t e = d.work.reserve(kWorkWords);
+  if (e == hipSuccess) e = hipMemset(d.work.p, 0, kWorkWords * sizeof(uint32_t));
   return e;
 }
 
@@ -1118,6 +1119,12 @@ struct WhatifUnits {
   const uint32_t* node_ptr = nullptr;
   const uint32_t* nodes = nullptr;
   uint32_t n_nodes = 0;  // entries of nodes
+  // metric events (edge_ptr != nullptr): event i gives edges[k] the metric metrics[k] for k in
+  // [edge_ptr[i], edge_ptr[i + 1])
+  const uint32_t* edge_ptr = nullptr;
+  const uint32_t* edges = nullptr;
+  const uint32_t* metrics = nullptr;
+  uint32_t n_edges = 0;  // entries of edges / metrics
 };
 
 // Drain sweep on one device (openr_spf_whatif_drain; spf_drain.hip has the unit semantics):
@@ -1197,9 +1204,84 @@ int check_drain(const openr_spf_ctx* ctx, uint32_t flags, uint64_t n_events, uin
   return OPENR_SPF_OK;
 }
 
+// Metric sweep on one device (openr_spf_whatif_metric; spf_metric.hip has the unit semantics):
+// base SPF with tight edges -> metric_filter (source-major list of the units with a raised
+// base-tight edge) -> the count read back (one stream sync) -> metric_repair, one workgroup
+// per listed unit on the base rows -> the units that outgrew its slots (a second 4-byte read)
+// through the same kernel with a slot per node. The caller has checked the plan and the LDS
+// sizes (check_metric) and serves the hop-count form itself: metrics do not enter it.
+hipError_t whatif_metric_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, const WhatifUnits& un,
+                                   const uint32_t* d_sources, uint32_t n_src, uint32_t* d_changed, hipStream_t s,
+                                   uint32_t* solved, bool use_link_metric, const WhatifDelta& dl) {
+  *solved = 0;
+  if (!n_src || !un.n) return hipSuccess;
+  const size_t units = (size_t)un.n * n_src;
+  if (units > 0xFFFFFFFFull || base_plan.exact || !use_link_metric) return hipErrorInvalidValue;
+  hipError_t err;
+#define OPENR_TRY(x)                   \
+  do {                                 \
+    if ((err = (x)) != hipSuccess) return err; \
+  } while (0)
+  bool base_tin = false;
+  OPENR_TRY(whatif_base_solve(ctx, d, base_plan, d_sources, n_src, s, &base_tin));
+  OPENR_TRY(d.wunit.reserve(units));
+  OPENR_TRY(d.wsrc.reserve(units));
+  OPENR_TRY(d.wcount.reserve(3));
+  MetricPass p{};
+  p.n_events = un.n;
+  p.n_edges = un.n_edges;
+  p.n_src = n_src;
+  p.nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
+  p.edge_ptr = un.edge_ptr;
+  p.edges = un.edges;
+  p.metrics = un.metrics;
+  p.sources = d_sources;
+  p.base_dist = d.base_dist.p;
+  p.base_nh = d.base_nh.p;
+  p.base_tight = d.base_tight.p;
+  p.base_tin = base_tin ? d.base_tin.p : nullptr;
+  p.changed = d_changed;
+  p.wunit = d.wunit.p;
+  p.ovf_unit = d.wsrc.p;
+  p.wcount = d.wcount.p;
+  p.ctr = d.work.p + kMetricCtr;
+  p.delta = dl;
+  OPENR_TRY(launch_metric_filter(d.g, p, d.num_cus, s));
+  uint32_t count = 0;
+  OPENR_TRY(hipMemcpyAsync(&count, d.wcount.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  OPENR_TRY(hipStreamSynchronize(s));
+  *solved = count;
+  if (!count) return hipSuccess;
+  OPENR_TRY(launch_metric_repair(d.g, p, count, false, d.num_cus, s));
+  uint32_t over = 0;
+  OPENR_TRY(hipMemcpyAsync(&over, d.wcount.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  OPENR_TRY(hipStreamSynchronize(s));
+  if (over) OPENR_TRY(launch_metric_repair(d.g, p, over, true, d.num_cus, s));
+#undef OPENR_TRY
+  return hipSuccess;
+}
+
+// Plan and capacity checks of the metric calls, as check_drain: the repair reads base_tight rows.
+int check_metric(const openr_spf_ctx* ctx, uint32_t flags, uint64_t n_events, uint64_t n_sources) {
+  if (n_events * n_sources > 0xFFFFFFFFull) return fail(OPENR_SPF_EINVAL, "more than 2^32 - 1 units");
+  Plan bp;
+  int rc = make_plan(ctx, flags, false, &bp);
+  if (rc) return rc;
+  if (bp.exact)
+    return fail(OPENR_SPF_ENOTSUP, "metric sweep needs a base plan outside the exact-order kernel (usable metrics in "
+                                   "[1, 2^31-1] under link metric, next-hop sets <= 256 bits)");
+  const uint32_t nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
+  if (!metric_lds_bytes(ctx->V, ctx->E, std::min(metric_slots(), ctx->V), nb) ||
+      !metric_lds_bytes(ctx->V, ctx->E, ctx->V, nb))
+    return fail(OPENR_SPF_E2BIG, "a metric unit's state does not fit LDS (V=%u, E=%u)", ctx->V, ctx->E);
+  return OPENR_SPF_OK;
+}
+
 hipError_t whatif_units_on_device(openr_spf_ctx* ctx, Device& d, const Plan& bp, const Plan& ip, const WhatifUnits& un,
                                   const uint32_t* d_sources, uint32_t n_src, uint32_t* d_changed, hipStream_t s,
                                   uint32_t* solved, bool use_link_metric, const WhatifDelta& dl = WhatifDelta{}) {
+  if (un.edge_ptr)
+    return whatif_metric_on_device(ctx, d, bp, un, d_sources, n_src, d_changed, s, solved, use_link_metric, dl);
   if (un.node_ptr)
     return whatif_drain_on_device(ctx, d, bp, un, d_sources, n_src, d_changed, s, solved, use_link_metric, dl);
   if (un.set_ptr)
@@ -1248,7 +1330,7 @@ int whatif_delta_on_device(openr_spf_ctx* ctx, Device& d, const WhatifUnits& un,
   dl.cap = (uint32_t)want;
   dl.nhb = nhb;
   dl.used = d.dl_used.p;
-  if (un.node_ptr && !cap) dl.node = nullptr;  // drain sweep, counts and ptr only: the repair writes no entries
+  if ((un.node_ptr || un.edge_ptr) && !cap) dl.node = nullptr;  // drain / metric sweep, counts and ptr only: the repair writes no entries
   uint32_t solved = 0;
   HIP_TRY(whatif_units_on_device(ctx, d, bp, ip, un, d_sources, n_src, d_changed, s, &solved,
                                  (flags & OPENR_SPF_USE_LINK_METRIC) != 0, dl));
@@ -1276,10 +1358,27 @@ int check_whatif_host(const openr_spf_ctx* ctx, const WhatifUnits& hu, const uin
                       const uint32_t* changed) {
   if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
   if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if ((hu.n && !hu.links && !hu.set_ptr && !hu.node_ptr) || (n_sources && !sources) || (hu.n && n_sources && !changed))
+  if ((hu.n && !hu.links && !hu.set_ptr && !hu.node_ptr && !hu.edge_ptr) || (n_sources && !sources) ||
+      (hu.n && n_sources && !changed))
     return fail(OPENR_SPF_EINVAL, "null links, sources or changed");
   for (uint32_t i = 0; i < n_sources; ++i)
     if (sources[i] >= ctx->V) return fail(OPENR_SPF_EINVAL, "source %u out of range (V=%u)", sources[i], ctx->V);
+  if (hu.edge_ptr) {  // metric events: raises only, ids strictly ascending inside an event
+    for (uint32_t i = 0; i < hu.n; ++i)
+      if (hu.edge_ptr[i + 1] < hu.edge_ptr[i]) return fail(OPENR_SPF_EINVAL, "edge_ptr does not ascend at event %u", i);
+    if (hu.edge_ptr[hu.n] > hu.edge_ptr[0] && (!hu.edges || !hu.metrics)) return fail(OPENR_SPF_EINVAL, "null edges or metrics");
+    for (uint32_t i = 0; i < hu.n; ++i)
+      for (uint32_t k = hu.edge_ptr[i]; k < hu.edge_ptr[i + 1]; ++k) {
+        const uint32_t e = hu.edges[k];
+        if (e >= ctx->E) return fail(OPENR_SPF_EINVAL, "edge %u out of range (E=%u)", e, ctx->E);
+        if (k > hu.edge_ptr[i] && e <= hu.edges[k - 1])
+          return fail(OPENR_SPF_EINVAL, "event %u: edge ids are not strictly ascending", i);
+        if (hu.metrics[k] < ctx->metric[e] || hu.metrics[k] > 0x7FFFFFFFu)
+          return fail(OPENR_SPF_EINVAL, "event %u: metric %u of edge %u is below the current one (%llu) or above 2^31-1",
+                      i, hu.metrics[k], e, (unsigned long long)ctx->metric[e]);
+      }
+    return OPENR_SPF_OK;
+  }
   if (hu.node_ptr) {  // drain events: the node CSR here, the link CSR (nullable) below
     for (uint32_t i = 0; i < hu.n; ++i)
       if (hu.node_ptr[i + 1] < hu.node_ptr[i]) return fail(OPENR_SPF_EINVAL, "node_ptr does not ascend at event %u", i);
@@ -1309,6 +1408,27 @@ int upload_whatif_units(Device& d, const WhatifUnits& hu, uint32_t b, uint32_t m
                         WhatifUnits* un) {
   *un = WhatifUnits{};
   un->n = m;
+  if (hu.edge_ptr) {  // metric events: edge CSR in win_ptr / win_edges / win_metrics
+    const uint32_t eb = hu.edge_ptr[b], ee = hu.edge_ptr[b + m];
+    rebased->resize(m + 1);
+    for (uint32_t i = 0; i <= m; ++i) (*rebased)[i] = hu.edge_ptr[b + i] - eb;
+    HIP_TRY(d.win_ptr.reserve(m + 1));
+    HIP_TRY(d.win_edges.reserve(std::max<uint32_t>(ee - eb, 1u)));
+    HIP_TRY(d.win_metrics.reserve(std::max<uint32_t>(ee - eb, 1u)));
+    HIP_TRY(hipMemcpyAsync(d.win_ptr.p, rebased->data(), (m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    if (ee > eb) {
+      HIP_TRY(hipMemcpyAsync(d.win_edges.p, hu.edges + eb, (ee - eb) * sizeof(uint32_t), hipMemcpyHostToDevice,
+                             d.stream));
+      HIP_TRY(hipMemcpyAsync(d.win_metrics.p, hu.metrics + eb, (ee - eb) * sizeof(uint32_t), hipMemcpyHostToDevice,
+                             d.stream));
+    }
+    HIP_TRY(hipStreamSynchronize(d.stream));  // `rebased` is reused for the next device's block
+    un->edge_ptr = d.win_ptr.p;
+    un->edges = d.win_edges.p;
+    un->metrics = d.win_metrics.p;
+    un->n_edges = ee - eb;
+    return OPENR_SPF_OK;
+  }
   if (hu.node_ptr) {  // drain events: node CSR in win_ptr / win_nodes, link CSR in win_lptr / win_links
     const uint32_t nb0 = hu.node_ptr[b], ne0 = hu.node_ptr[b + m];
     rebased->resize(m + 1);
@@ -1503,7 +1623,8 @@ int whatif_device_form(openr_spf_ctx* ctx, int device_index, const WhatifUnits& 
   if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
   if (device_index < 0 || device_index >= (int)ctx->devs.size())
     return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
-  if ((un.n && !un.links && !un.set_ptr && !un.node_ptr) || (n_sources && !d_sources) || (un.n && n_sources && !d_changed))
+  if ((un.n && !un.links && !un.set_ptr && !un.node_ptr && !un.edge_ptr) || (n_sources && !d_sources) ||
+      (un.n && n_sources && !d_changed))
     return fail(OPENR_SPF_EINVAL, "null links, sources or changed");
   Plan bp, ip;
   int rc = whatif_plans(ctx, flags, &bp, &ip);
@@ -1530,7 +1651,8 @@ int whatif_delta_device_form(openr_spf_ctx* ctx, int device_index, const WhatifU
   if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
   if (device_index < 0 || device_index >= (int)ctx->devs.size())
     return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
-  if ((un.n && !un.links && !un.set_ptr && !un.node_ptr) || (n_sources && !d_sources) || (un.n && n_sources && !d_changed) || !d_ptr)
+  if ((un.n && !un.links && !un.set_ptr && !un.node_ptr && !un.edge_ptr) || (n_sources && !d_sources) ||
+      (un.n && n_sources && !d_changed) || !d_ptr)
     return fail(OPENR_SPF_EINVAL, "null links, sources, changed or ptr");
   if (cap && (!d_node || !d_dist || !d_nh)) return fail(OPENR_SPF_EINVAL, "null delta buffer");
   Device& d = ctx->devs[device_index];
@@ -1587,6 +1709,30 @@ int check_drain_events(const openr_spf_ctx* ctx, const openr_spf_drain_events_t*
 
 WhatifUnits host_drain(const openr_spf_drain_events_t* ev) {
   return drain_units(ev->node_ptr, ev->nodes, ev->link_ptr, ev->links, ev->n_events, 0u, 0u);
+}
+
+// Metric events as what-if units (host or device memory; n_edges: the device form's slice length).
+WhatifUnits metric_units(const uint32_t* edge_ptr, const uint32_t* edges, const uint32_t* metrics, uint32_t n_events,
+                         uint32_t n_edges) {
+  WhatifUnits un;
+  un.edge_ptr = n_events ? edge_ptr : nullptr;
+  un.edges = edges;
+  un.metrics = metrics;
+  un.n_edges = n_edges;
+  un.n = n_events;
+  return un;
+}
+
+int check_metric_events(const openr_spf_ctx* ctx, const openr_spf_metric_events_t* ev) {
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (!ev) return fail(OPENR_SPF_EINVAL, "null events");
+  if (ev->n_events && !ev->edge_ptr) return fail(OPENR_SPF_EINVAL, "null edge_ptr");
+  return OPENR_SPF_OK;
+}
+
+WhatifUnits host_metric(const openr_spf_metric_events_t* ev) {
+  return metric_units(ev->edge_ptr, ev->edges, ev->metrics, ev->n_events, 0u);
 }
 
 // ---- route-level calls (spf_routes.hip) ---------------------------------------------------
@@ -3533,6 +3679,131 @@ int openr_spf_whatif_drain_routes_device(openr_spf_ctx* ctx, int device_index, c
                                d_sources, n_sources, flags, gr, d_changed_routes, d_ptr, d_group, d_metric, d_nh,
                                d_n_best, cap, nh_bytes, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream,
                                &total, &solved);
+  if (out_total) *out_total = total;
+  if (out_solved) *out_solved = solved;
+  return rc;
+}
+
+// The hop-count form of a metric sweep: metrics do not enter runSpf(src, false), so every
+// count is 0 and ptr is all zero. No kernel is launched.
+static int metric_hops_device(openr_spf_ctx* ctx, int device_index, uint32_t n_events, uint32_t n_sources,
+                              uint32_t* d_changed, uint64_t* d_ptr, void* stream, uint64_t* out_total,
+                              uint64_t* out_solved) {
+  Device& d = ctx->devs[device_index];
+  HIP_TRY(hipSetDevice(d.ordinal));
+  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d.stream;
+  const size_t units = (size_t)n_events * n_sources;
+  if (units) HIP_TRY(hipMemsetAsync(d_changed, 0, units * sizeof(uint32_t), s));
+  HIP_TRY(hipMemsetAsync(d_ptr, 0, (units + 1) * sizeof(uint64_t), s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (out_total) *out_total = 0;
+  if (out_solved) *out_solved = 0;
+  return OPENR_SPF_OK;
+}
+
+int openr_spf_whatif_metric(openr_spf_ctx* ctx, const openr_spf_metric_events_t* events, const uint32_t* sources,
+                            uint32_t n_sources, uint32_t flags, uint32_t* changed, openr_spf_whatif_delta_t* delta,
+                            uint64_t* out_solved) {
+  clear_launch_trace();
+  int rc = check_metric_events(ctx, events);
+  if (rc) return rc;
+  const WhatifUnits hu = host_metric(events);
+  if ((rc = check_whatif_host(ctx, hu, sources, n_sources, changed)) != OPENR_SPF_OK) return rc;
+  if ((rc = check_metric(ctx, flags, events->n_events, n_sources)) != OPENR_SPF_OK) return rc;
+  if (!(flags & OPENR_SPF_USE_LINK_METRIC)) {
+    if (delta && !delta->ptr) return fail(OPENR_SPF_EINVAL, "null delta->ptr");
+    const size_t units = (size_t)events->n_events * n_sources;
+    if (units) std::memset(changed, 0, units * sizeof(uint32_t));
+    if (delta) std::memset(delta->ptr, 0, (units + 1) * sizeof(uint64_t));
+    if (out_solved) *out_solved = 0;
+    return OPENR_SPF_OK;
+  }
+  if (!delta) return whatif_host(ctx, hu, sources, n_sources, flags, changed, out_solved);
+  return whatif_delta_host(ctx, hu, sources, n_sources, flags, changed, delta, out_solved);
+}
+
+int openr_spf_whatif_metric_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_edge_ptr,
+                                   const uint32_t* d_edges, const uint32_t* d_metrics, uint32_t n_events,
+                                   uint32_t n_edges, const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                                   uint32_t* d_changed, uint64_t* d_ptr, uint32_t* d_node, uint64_t* d_dist,
+                                   uint8_t* d_nh, uint64_t cap, uint32_t nh_bytes, void* stream, uint64_t* out_total,
+                                   uint64_t* out_solved) {
+  clear_launch_trace();
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (n_events && (!d_edge_ptr || (n_edges && (!d_edges || !d_metrics))))
+    return fail(OPENR_SPF_EINVAL, "null edge_ptr, edges or metrics");
+  int rc = check_metric(ctx, flags, n_events, n_sources);
+  if (rc) return rc;
+  if (!(flags & OPENR_SPF_USE_LINK_METRIC)) {
+    if (device_index < 0 || device_index >= (int)ctx->devs.size())
+      return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+    if ((n_sources && !d_sources) || (n_events && n_sources && !d_changed) || !d_ptr)
+      return fail(OPENR_SPF_EINVAL, "null sources, changed or ptr");
+    return metric_hops_device(ctx, device_index, n_events, n_sources, d_changed, d_ptr, stream, out_total, out_solved);
+  }
+  return whatif_delta_device_form(ctx, device_index, metric_units(d_edge_ptr, d_edges, d_metrics, n_events, n_edges),
+                                  d_sources, n_sources, flags, d_changed, d_ptr, d_node, d_dist, d_nh, cap, nh_bytes,
+                                  stream, out_total, out_solved);
+}
+
+int openr_spf_whatif_metric_routes(openr_spf_ctx* ctx, const openr_spf_metric_events_t* events,
+                                   const uint32_t* sources, uint32_t n_sources, uint32_t flags,
+                                   const openr_spf_groups_t* groups, uint32_t* changed_routes,
+                                   openr_spf_whatif_routes_t* delta, uint64_t* out_solved) {
+  clear_launch_trace();
+  int rc = check_metric_events(ctx, events);
+  if (rc) return rc;
+  const WhatifUnits hu = host_metric(events);
+  if ((rc = check_whatif_host(ctx, hu, sources, n_sources, changed_routes)) != OPENR_SPF_OK) return rc;
+  if ((rc = check_metric(ctx, flags, events->n_events, n_sources)) != OPENR_SPF_OK) return rc;
+  if (!(flags & OPENR_SPF_USE_LINK_METRIC)) {
+    if ((rc = check_groups_host(ctx, groups)) != OPENR_SPF_OK) return rc;
+    if (delta && !delta->ptr) return fail(OPENR_SPF_EINVAL, "null delta->ptr");
+    const size_t units = (size_t)events->n_events * n_sources;
+    if (units) std::memset(changed_routes, 0, units * sizeof(uint32_t));
+    if (delta) std::memset(delta->ptr, 0, (units + 1) * sizeof(uint64_t));
+    if (out_solved) *out_solved = 0;
+    return OPENR_SPF_OK;
+  }
+  return whatif_routes_host(ctx, hu, sources, n_sources, flags, groups, changed_routes, delta, out_solved);
+}
+
+int openr_spf_whatif_metric_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_edge_ptr,
+                                          const uint32_t* d_edges, const uint32_t* d_metrics, uint32_t n_events,
+                                          uint32_t n_edges, const uint32_t* d_sources, uint32_t n_sources,
+                                          uint32_t flags, const uint32_t* d_group_ptr, const uint32_t* d_group_nodes,
+                                          uint32_t n_groups, uint32_t n_group_nodes, uint32_t* d_changed_routes,
+                                          uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
+                                          uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes, void* stream,
+                                          uint64_t* out_total, uint64_t* out_solved) {
+  clear_launch_trace();
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (device_index < 0 || device_index >= (int)ctx->devs.size())
+    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+  if ((n_events && (!d_edge_ptr || (n_edges && (!d_edges || !d_metrics)))) || (n_sources && !d_sources) ||
+      (n_events && n_sources && !d_changed_routes) || !d_ptr)
+    return fail(OPENR_SPF_EINVAL, "null events, sources, changed_routes or ptr");
+  if ((n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes))
+    return fail(OPENR_SPF_EINVAL, "null group_ptr or group_nodes");
+  if (cap && (!d_group || !d_metric || !d_nh)) return fail(OPENR_SPF_EINVAL, "null route buffer");
+  int rc = check_metric(ctx, flags, n_events, n_sources);
+  if (rc) return rc;
+  if (!(flags & OPENR_SPF_USE_LINK_METRIC))
+    return metric_hops_device(ctx, device_index, n_events, n_sources, d_changed_routes, d_ptr, stream, out_total,
+                              out_solved);
+  Device& d = ctx->devs[device_index];
+  HIP_TRY(hipSetDevice(d.ordinal));
+  DevGroups gr;
+  gr.ptr = d_group_ptr;
+  gr.nodes = d_group_nodes;
+  gr.n = n_groups;
+  gr.m = n_group_nodes;
+  uint64_t total = 0, solved = 0;
+  rc = whatif_routes_on_device(ctx, d, metric_units(d_edge_ptr, d_edges, d_metrics, n_events, n_edges), d_sources,
+                               n_sources, flags, gr, d_changed_routes, d_ptr, d_group, d_metric, d_nh, d_n_best, cap,
+                               nh_bytes, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream, &total, &solved);
   if (out_total) *out_total = total;
   if (out_solved) *out_solved = solved;
   return rc;

@@ -504,6 +504,47 @@ hipError_t launch_drain_filter(const DevGraph& g, const DrainPass& p, int num_cu
 hipError_t launch_drain_repair(const DevGraph& g, const DrainPass& p, uint32_t count, bool rerun, int num_cus,
                                hipStream_t s);
 
+// Metric what-if sweep (spf_metric.hip): unit u = i * n_src + j raises the metrics of event
+// i's directed edges (edges[edge_ptr[i], edge_ptr[i + 1]), ids ascending, metrics[k] the new
+// metric of edges[k]) for sources[j]; the rule is in that file's header and at
+// openr_spf_whatif_metric. Slices are clamped to n_edges entries; an entry whose id is out
+// of range, whose edge is down or whose metric is not in (current, 2^31 - 1] is skipped.
+struct MetricPass {
+  uint32_t n_events, n_edges, n_src, nb;
+  const uint32_t* edge_ptr;
+  const uint32_t* edges;
+  const uint32_t* metrics;
+  const uint32_t* sources;
+  const uint64_t* base_dist;   // base rows [n_src][V] (whatif_base_solve)
+  const uint8_t* base_nh;      // [n_src][V][nb]
+  const uint64_t* base_tight;  // [n_src][ceil(E / 64)]
+  const uint16_t* base_tin;    // nullable [n_src][V] tight in-degrees (rounds plan)
+  uint32_t* changed;           // [units]
+  uint32_t* wunit;             // [units] affected units
+  uint32_t* ovf_unit;          // [units] units that outgrew the narrow launch's slots
+  uint32_t* wcount;            // [2] affected units, overflowed units
+  uint32_t* ctr;               // 2 work counters (zero at rest)
+  WhatifDelta delta;           // node == null: counts only
+};
+constexpr uint32_t kMetricCtr = kDrainCtr + 2;
+constexpr uint32_t kWorkWords = kMetricCtr + 2;  // the counter buffer: the class blocks, then one pair per sweep kernel
+static_assert(kDrainCtr + 2 == kWorkSlots, "the metric sweep's counters follow the last class block");
+constexpr uint32_t kMetricSlots = 256;      // dirty-node slots of the narrow launch (OPENR_SPF_METRIC_SLOTS)
+constexpr uint32_t kMetricBlock = 64;       // threads per unit, narrow launch
+constexpr uint32_t kMetricBlockWide = 256;  // ... and the re-run with a slot per node
+uint32_t metric_slots();
+// LDS of a unit with S slots; 0 when it does not fit kMaxLds (or S outgrows the u16 index).
+// The drain layout without its node and link bitmaps (X, K), plus E bits for the raised edges.
+uint32_t metric_lds_bytes(uint32_t V, uint32_t E, uint32_t S, uint32_t nb);
+// changed[u] = 0 for every unit; the units with a raised base-tight edge are appended
+// source-major to wunit, wcount[0] of them; wcount[1] = 0.
+hipError_t launch_metric_filter(const DevGraph& g, const MetricPass& p, int num_cus, hipStream_t s);
+// Repairs wunit[0, count): changed[] and the delta of every listed unit; units past the
+// slots are appended to ovf_unit (wcount[1]). rerun: repairs ovf_unit[0, count) with a slot
+// per node instead (nothing overflows).
+hipError_t launch_metric_repair(const DevGraph& g, const MetricPass& p, uint32_t count, bool rerun, int num_cus,
+                                hipStream_t s);
+
 // Incremental mirror updates (spf_update.hip).
 // In-place attribute patch of the device mirror: each record overwrites one element of
 // one DevGraph array (structure — rows, columns, link ids — never changes).

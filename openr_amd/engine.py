@@ -62,6 +62,10 @@ EXPORTS = (
     "openr_spf_whatif_drain_device",
     "openr_spf_whatif_drain_routes",
     "openr_spf_whatif_drain_routes_device",
+    "openr_spf_whatif_metric",
+    "openr_spf_whatif_metric_device",
+    "openr_spf_whatif_metric_routes",
+    "openr_spf_whatif_metric_routes_device",
     "openr_spf_ksp2",
     "openr_spf_ksp2_device",
     "openr_spf_host_alloc",
@@ -171,6 +175,15 @@ class DrainEvents(ctypes.Structure):  # openr_spf_drain_events_t
     ]
 
 
+class MetricEvents(ctypes.Structure):  # openr_spf_metric_events_t
+    _fields_ = [
+        ("n_events", ctypes.c_uint32),
+        ("edge_ptr", ctypes.c_void_p),
+        ("edges", ctypes.c_void_p),
+        ("metrics", ctypes.c_void_p),
+    ]
+
+
 class SpfLimits(ctypes.Structure):
     _fields_ = [("max_nodes", ctypes.c_uint32), ("max_nh_bits", ctypes.c_uint32)]
 
@@ -253,6 +266,15 @@ def load_library():
     l.openr_spf_whatif_drain_routes_device.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, u32, u32, u32, vp, u32, u32,
                                                        vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, ctypes.c_uint64,
                                                        u32, vp, P(ctypes.c_uint64), P(ctypes.c_uint64)]
+    l.openr_spf_whatif_metric.argtypes = [vp, P(MetricEvents), vp, u32, u32, vp, P(WhatifDelta), P(ctypes.c_uint64)]
+    l.openr_spf_whatif_metric_device.argtypes = [vp, ctypes.c_int, vp, vp, vp, u32, u32, vp, u32, u32, vp, vp, vp, vp,
+                                                 vp, ctypes.c_uint64, u32, vp, P(ctypes.c_uint64),
+                                                 P(ctypes.c_uint64)]
+    l.openr_spf_whatif_metric_routes.argtypes = [vp, P(MetricEvents), vp, u32, u32, P(SpfGroups), vp, P(WhatifRoutes),
+                                                 P(ctypes.c_uint64)]
+    l.openr_spf_whatif_metric_routes_device.argtypes = [vp, ctypes.c_int, vp, vp, vp, u32, u32, vp, u32, u32, vp, vp,
+                                                        u32, u32, vp, vp, vp, vp, vp, vp, ctypes.c_uint64, u32, vp,
+                                                        P(ctypes.c_uint64), P(ctypes.c_uint64)]
     l.openr_spf_ksp2.argtypes = [vp, vp, vp, u32, u32, vp, vp]
     l.openr_spf_ksp2_device.argtypes = [vp, ctypes.c_int, vp, u32, vp, vp, u32, u32, vp, vp, vp]
     l.openr_spf_host_alloc.argtypes = [ctypes.c_size_t, P(vp)]
@@ -850,6 +872,119 @@ class SpfEngine:
             vp(d_group_ptr or None), vp(d_group_nodes or None), n_groups, n_group_nodes, vp(d_changed), vp(d_ptr),
             vp(d_group or None), vp(d_metric or None), vp(d_nh or None), vp(d_n_best or None), cap, nh_bytes,
             vp(stream or None), ctypes.byref(total), ctypes.byref(solved))
+        if not (allow_overflow and rc == E2BIG):
+            _check(rc)
+        return int(total.value), int(solved.value)
+
+    @staticmethod
+    def _metric_events(edge_sets: Sequence[Sequence[int]], metric_sets: Sequence[Sequence[int]]):
+        """(MetricEvents, the arrays it points into) of per-event edge and new-metric lists (as
+        given: topology.metric_events sorts and merges them)."""
+        n = len(edge_sets)
+        if len(metric_sets) != n or any(len(e) != len(m) for e, m in zip(edge_sets, metric_sets)):
+            raise ValueError("edge_sets and metric_sets differ in length")
+        ep, ee = _ignore_arrays(edge_sets, n)
+        _, mm = _ignore_arrays(metric_sets, n)
+        return MetricEvents(n, _p(ep), _p(ee), _p(mm)), (ep, ee, mm)
+
+    def whatif_metric(self, edge_sets: Sequence[Sequence[int]], metric_sets: Sequence[Sequence[int]],
+                      sources: Sequence[int], want_delta: bool = True, use_link_metric: bool = True,
+                      cap: Optional[int] = None, nh_bytes: Optional[int] = None):
+        """Metric sweep (openr_spf_whatif_metric): event i gives the directed edge edge_sets[i][k]
+        the metric metric_sets[i][k] (raises only, edge ids strictly ascending: see
+        topology.metric_events / soft_drain_events); unit u = i * n_sources + j. Returns the
+        shape of whatif_drain: (changed[n_events, n_sources] u32, ptr, node, dist, nh, solved),
+        or (changed, solved) with want_delta=False. cap None: sized from a count-only pass."""
+        ev, keep = self._metric_events(edge_sets, metric_sets)
+        n = len(edge_sets)
+        src = np.ascontiguousarray(sources, dtype=np.uint32)
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
+        solved = ctypes.c_uint64()
+        if not want_delta or cap is None:
+            _check(self._lib.openr_spf_whatif_metric(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
+                                                     _p(changed), None, ctypes.byref(solved)))
+            if not want_delta:
+                return changed, int(solved.value)
+            cap = int(changed.sum(dtype=np.uint64))
+        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
+        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
+        node = np.zeros(max(cap, 1), dtype=np.uint32)
+        dist = np.zeros(max(cap, 1), dtype=np.uint64)
+        nh = np.zeros((max(cap, 1), nb), dtype=np.uint8)
+        d = WhatifDelta(_p(ptr), _p(node), _p(dist), _p(nh), cap, nb)
+        _check(self._lib.openr_spf_whatif_metric(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
+                                                 _p(changed), ctypes.byref(d), ctypes.byref(solved)))
+        del keep
+        k = int(ptr[-1])
+        return changed, ptr, node[:k], dist[:k], nh[:k], int(solved.value)
+
+    def whatif_metric_device(self, d_edge_ptr: int, d_edges: int, d_metrics: int, n_events: int, n_edges: int,
+                             d_sources: int, n_sources: int, d_changed: int, d_ptr: int, d_node: int, d_dist: int,
+                             d_nh: int, cap: int, nh_bytes: int, use_link_metric: bool = True, stream: int = 0,
+                             device_index: int = 0, allow_overflow: bool = False) -> Tuple[int, int]:
+        """Device-pointer form: (total entries, solved). d_ptr [n_units + 1] u64 CSR; unit u's
+        entries are [ptr[u], ptr[u + 1]) in the kernel's order."""
+        vp = ctypes.c_void_p
+        total = ctypes.c_uint64()
+        solved = ctypes.c_uint64()
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        rc = self._lib.openr_spf_whatif_metric_device(
+            self._ctx, device_index, vp(d_edge_ptr or None), vp(d_edges or None), vp(d_metrics or None), n_events,
+            n_edges, vp(d_sources), n_sources, flags, vp(d_changed), vp(d_ptr), vp(d_node or None),
+            vp(d_dist or None), vp(d_nh or None), cap, nh_bytes, vp(stream or None), ctypes.byref(total),
+            ctypes.byref(solved))
+        if not (allow_overflow and rc == E2BIG):
+            _check(rc)
+        return int(total.value), int(solved.value)
+
+    def whatif_metric_routes(self, edge_sets: Sequence[Sequence[int]], metric_sets: Sequence[Sequence[int]],
+                             sources: Sequence[int], groups: Sequence[Sequence[int]], use_link_metric: bool = True,
+                             cap: Optional[int] = None, nh_bytes: Optional[int] = None):
+        """The metric sweep resolved to routes (openr_spf_whatif_metric_routes): the return shape
+        of whatif_routes. cap None: sized from a count-only pass."""
+        ev, keep = self._metric_events(edge_sets, metric_sets)
+        n = len(edge_sets)
+        gp, gn = _ignore_arrays(groups, len(groups))
+        gs = SpfGroups(len(groups), _p(gp), _p(gn))
+        src = np.ascontiguousarray(sources, dtype=np.uint32)
+        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
+        solved = ctypes.c_uint64()
+        if cap is None:
+            _check(self._lib.openr_spf_whatif_metric_routes(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
+                                                            ctypes.byref(gs), _p(changed), None, ctypes.byref(solved)))
+            cap = int(changed.sum(dtype=np.uint64))
+        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
+        group = np.zeros(max(cap, 1), dtype=np.uint32)
+        metric = np.zeros(max(cap, 1), dtype=np.uint64)
+        nh = np.zeros((max(cap, 1), nb), dtype=np.uint8)
+        n_best = np.zeros(max(cap, 1), dtype=np.uint32)
+        d = WhatifRoutes(_p(ptr), _p(group), _p(metric), _p(nh), _p(n_best), cap, nb)
+        _check(self._lib.openr_spf_whatif_metric_routes(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
+                                                        ctypes.byref(gs), _p(changed), ctypes.byref(d),
+                                                        ctypes.byref(solved)))
+        del keep
+        k = int(ptr[-1])
+        return changed, ptr, group[:k], metric[:k], nh[:k], n_best[:k], int(solved.value)
+
+    def whatif_metric_routes_device(self, d_edge_ptr: int, d_edges: int, d_metrics: int, n_events: int, n_edges: int,
+                                    d_sources: int, n_sources: int, d_group_ptr: int, d_group_nodes: int,
+                                    n_groups: int, n_group_nodes: int, d_changed: int, d_ptr: int, d_group: int,
+                                    d_metric: int, d_nh: int, d_n_best: int, cap: int, nh_bytes: int,
+                                    use_link_metric: bool = True, stream: int = 0, device_index: int = 0,
+                                    allow_overflow: bool = False) -> Tuple[int, int]:
+        """Device-pointer form: (total entries, solved); outputs as whatif_routes_device."""
+        vp = ctypes.c_void_p
+        total = ctypes.c_uint64()
+        solved = ctypes.c_uint64()
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        rc = self._lib.openr_spf_whatif_metric_routes_device(
+            self._ctx, device_index, vp(d_edge_ptr or None), vp(d_edges or None), vp(d_metrics or None), n_events,
+            n_edges, vp(d_sources), n_sources, flags, vp(d_group_ptr or None), vp(d_group_nodes or None), n_groups,
+            n_group_nodes, vp(d_changed), vp(d_ptr), vp(d_group or None), vp(d_metric or None), vp(d_nh or None),
+            vp(d_n_best or None), cap, nh_bytes, vp(stream or None), ctypes.byref(total), ctypes.byref(solved))
         if not (allow_overflow and rc == E2BIG):
             _check(rc)
         return int(total.value), int(solved.value)

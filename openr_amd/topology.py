@@ -506,6 +506,61 @@ def drain_events(g: CsrGraph, node_sets: Iterable[Iterable[int]],
     return nodes, links
 
 
+def metric_events(g: CsrGraph, edge_sets: Iterable[Iterable[int]], metric_sets: Iterable[Iterable[int]]):
+    """Metric events for ``SpfEngine.whatif_metric`` / ``whatif_metric_routes``: per event the
+    directed CSR edges and the new metric of each. Every entry is validated (edge ids in
+    [0, num_dir_edges), new metric in [current metric, 2^31 - 1]); an event is sorted by edge
+    id, and an edge listed twice keeps the larger metric. Returns (edge_sets, metric_sets)."""
+    edge_sets = [list(x) for x in edge_sets]
+    metric_sets = [list(x) for x in metric_sets]
+    if len(edge_sets) != len(metric_sets):
+        raise ValueError(f"{len(edge_sets)} edge sets but {len(metric_sets)} metric sets")
+    E = g.num_dir_edges
+    out_e, out_m = [], []
+    for k, (edges, metrics) in enumerate(zip(edge_sets, metric_sets)):
+        if len(edges) != len(metrics):
+            raise ValueError(f"event {k}: {len(edges)} edges but {len(metrics)} metrics")
+        best: Dict[int, int] = {}
+        for e, m in zip(edges, metrics):
+            e, m = int(e), int(m)
+            if not 0 <= e < E:
+                raise ValueError(f"event {k}: edge {e} out of range (E={E})")
+            if m < int(g.metric[e]):
+                raise ValueError(f"event {k}: metric {m} of edge {e} is below the current one ({int(g.metric[e])})")
+            if m > 0x7FFFFFFF:
+                raise ValueError(f"event {k}: metric {m} of edge {e} is above 2^31 - 1")
+            best[e] = max(m, best.get(e, m))
+        ids = sorted(best)
+        out_e.append(ids)
+        out_m.append([best[e] for e in ids])
+    return out_e, out_m
+
+
+def soft_drain_events(g: CsrGraph, node_sets: Iterable[Iterable[int]], increment: int,
+                      both_directions: bool = False):
+    """Soft drains as metric events: event i raises every adjacency the nodes of node_sets[i]
+    advertise (their CSR rows) by ``increment``; with ``both_directions`` also the reverse of
+    each, the other directed edge with the same link id. Returns (edge_sets, metric_sets) as
+    ``metric_events`` does."""
+    if increment < 0:
+        raise ValueError("a soft drain raises metrics: increment must be >= 0")
+    rev = None
+    if both_directions:
+        if np.any(np.bincount(g.link_id, minlength=g.num_links) != 2):
+            raise ValueError("a link without exactly two directed edges")
+        pair = np.argsort(g.link_id, kind="stable").reshape(-1, 2)  # the two directed edges of each link
+        rev = np.empty(g.num_dir_edges, dtype=np.int64)
+        rev[pair[:, 0]], rev[pair[:, 1]] = pair[:, 1], pair[:, 0]
+    edge_sets, metric_sets = [], []
+    for nodes in prefix_groups(g, node_sets):
+        edges = [e for u in nodes for e in g.row(u)]
+        if rev is not None:
+            edges += [int(rev[e]) for e in edges]
+        edge_sets.append(edges)
+        metric_sets.append([int(g.metric[e]) + increment for e in edges])
+    return metric_events(g, edge_sets, metric_sets)
+
+
 def prefix_groups(g: CsrGraph, groups: Iterable[Iterable[int]]) -> List[List[int]]:
     """Caller-given prefix groups (the advertisers of each prefix) as a group table for
     ``SpfEngine.routes`` / ``whatif_routes``: every group validated (node ids in
