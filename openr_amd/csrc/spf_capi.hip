@@ -1127,18 +1127,22 @@ struct WhatifUnits {
   uint32_t n_edges = 0;  // entries of edges / metrics
 };
 
-// Drain sweep on one device (openr_spf_whatif_drain; spf_drain.hip has the unit semantics):
-// base SPF with tight edges -> drain_filter (source-major list of the units with a removed
-// base-tight edge) -> the count read back (one stream sync) -> drain_repair, one workgroup
-// per listed unit on the base rows -> the units that outgrew its slots (a second 4-byte read)
-// through the same kernel with a slot per node. The caller has checked the plan and the LDS
-// sizes (check_drain).
-hipError_t whatif_drain_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, const WhatifUnits& un,
-                                  const uint32_t* d_sources, uint32_t n_src, uint32_t* d_changed, hipStream_t s,
-                                  uint32_t* solved, bool use_link_metric, const WhatifDelta& dl) {
+// Event sweep on one device (openr_spf_whatif_drain / _metric; spf_drain.hip and spf_metric.hip
+// have the unit semantics): base SPF with tight edges -> the filter (source-major list of the
+// units with a hit base-tight edge) -> the count read back (one stream sync) -> the repair,
+// one workgroup per listed unit on the base rows -> the units that outgrew its slots (a
+// second 4-byte read) through the same kernel with a slot per node. `p` arrives with its
+// event CSR filled; the common part is filled here. The caller has checked the plan and the
+// LDS sizes (check_repair_sweep).
+template <class Pass>
+hipError_t whatif_repair_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, Pass& p, uint32_t n_events,
+                                   uint32_t ctr, hipError_t (*filter)(const DevGraph&, const Pass&, int, hipStream_t),
+                                   hipError_t (*repair)(const DevGraph&, const Pass&, uint32_t, bool, int, hipStream_t),
+                                   const uint32_t* d_sources, uint32_t n_src, uint32_t* d_changed, hipStream_t s,
+                                   uint32_t* solved, const WhatifDelta& dl) {
   *solved = 0;
-  if (!n_src || !un.n) return hipSuccess;
-  const size_t units = (size_t)un.n * n_src;
+  if (!n_src || !n_events) return hipSuccess;
+  const size_t units = (size_t)n_events * n_src;
   if (units > 0xFFFFFFFFull || base_plan.exact) return hipErrorInvalidValue;
   hipError_t err;
 #define OPENR_TRY(x)                   \
@@ -1150,131 +1154,90 @@ hipError_t whatif_drain_on_device(openr_spf_ctx* ctx, Device& d, const Plan& bas
   OPENR_TRY(d.wunit.reserve(units));
   OPENR_TRY(d.wsrc.reserve(units));
   OPENR_TRY(d.wcount.reserve(3));
-  DrainPass p{};
-  p.n_events = un.n;
-  p.n_nodes = un.n_nodes;
-  p.n_links = un.n_set_links;
+  p.n_events = n_events;
   p.n_src = n_src;
   p.nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
+  p.sources = d_sources;
+  p.base_dist = d.base_dist.p;
+  p.base_nh = d.base_nh.p;
+  p.base_tight = d.base_tight.p;
+  p.base_tin = base_tin ? d.base_tin.p : nullptr;
+  p.changed = d_changed;
+  p.wunit = d.wunit.p;
+  p.ovf_unit = d.wsrc.p;
+  p.wcount = d.wcount.p;
+  p.ctr = d.work.p + ctr;
+  p.delta = dl;
+  OPENR_TRY(filter(d.g, p, d.num_cus, s));
+  uint32_t count = 0;
+  OPENR_TRY(hipMemcpyAsync(&count, d.wcount.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  OPENR_TRY(hipStreamSynchronize(s));
+  *solved = count;
+  if (!count) return hipSuccess;
+  OPENR_TRY(repair(d.g, p, count, false, d.num_cus, s));
+  uint32_t over = 0;
+  OPENR_TRY(hipMemcpyAsync(&over, d.wcount.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  OPENR_TRY(hipStreamSynchronize(s));
+  if (over) OPENR_TRY(repair(d.g, p, over, true, d.num_cus, s));
+#undef OPENR_TRY
+  return hipSuccess;
+}
+
+hipError_t whatif_drain_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, const WhatifUnits& un,
+                                  const uint32_t* d_sources, uint32_t n_src, uint32_t* d_changed, hipStream_t s,
+                                  uint32_t* solved, bool use_link_metric, const WhatifDelta& dl) {
+  DrainPass p{};
+  p.n_nodes = un.n_nodes;
+  p.n_links = un.n_set_links;
   p.unit_cost = use_link_metric ? 0u : 1u;
   p.node_ptr = un.node_ptr;
   p.nodes = un.nodes;
   p.link_ptr = un.set_ptr;
   p.links = un.set_links;
-  p.sources = d_sources;
-  p.base_dist = d.base_dist.p;
-  p.base_nh = d.base_nh.p;
-  p.base_tight = d.base_tight.p;
-  p.base_tin = base_tin ? d.base_tin.p : nullptr;
-  p.changed = d_changed;
-  p.wunit = d.wunit.p;
-  p.ovf_unit = d.wsrc.p;
-  p.wcount = d.wcount.p;
-  p.ctr = d.work.p + kDrainCtr;
-  p.delta = dl;
-  OPENR_TRY(launch_drain_filter(d.g, p, d.num_cus, s));
-  uint32_t count = 0;
-  OPENR_TRY(hipMemcpyAsync(&count, d.wcount.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  OPENR_TRY(hipStreamSynchronize(s));
-  *solved = count;
-  if (!count) return hipSuccess;
-  OPENR_TRY(launch_drain_repair(d.g, p, count, false, d.num_cus, s));
-  uint32_t over = 0;
-  OPENR_TRY(hipMemcpyAsync(&over, d.wcount.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  OPENR_TRY(hipStreamSynchronize(s));
-  if (over) OPENR_TRY(launch_drain_repair(d.g, p, over, true, d.num_cus, s));
-#undef OPENR_TRY
-  return hipSuccess;
+  return whatif_repair_on_device(ctx, d, base_plan, p, un.n, kDrainCtr, launch_drain_filter, launch_drain_repair,
+                                 d_sources, n_src, d_changed, s, solved, dl);
 }
 
-// Plan and capacity checks of the drain calls: the repair reads base_tight rows, which the
-// exact-order kernel's history-dependent pop order does not give a meaning the rule can use.
-int check_drain(const openr_spf_ctx* ctx, uint32_t flags, uint64_t n_events, uint64_t n_sources) {
-  if (n_events * n_sources > 0xFFFFFFFFull) return fail(OPENR_SPF_EINVAL, "more than 2^32 - 1 units");
-  Plan bp;
-  int rc = make_plan(ctx, flags, false, &bp);
-  if (rc) return rc;
-  if (bp.exact)
-    return fail(OPENR_SPF_ENOTSUP, "drain sweep needs a base plan outside the exact-order kernel (usable metrics in "
-                                   "[1, 2^31-1] under link metric, next-hop sets <= 256 bits)");
-  const uint32_t nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
-  if (!drain_lds_bytes(ctx->V, ctx->L, std::min(drain_slots(), ctx->V), nb) ||
-      !drain_lds_bytes(ctx->V, ctx->L, ctx->V, nb))
-    return fail(OPENR_SPF_E2BIG, "a drain unit's state does not fit LDS (V=%u, L=%u)", ctx->V, ctx->L);
-  return OPENR_SPF_OK;
-}
-
-// Metric sweep on one device (openr_spf_whatif_metric; spf_metric.hip has the unit semantics):
-// base SPF with tight edges -> metric_filter (source-major list of the units with a raised
-// base-tight edge) -> the count read back (one stream sync) -> metric_repair, one workgroup
-// per listed unit on the base rows -> the units that outgrew its slots (a second 4-byte read)
-// through the same kernel with a slot per node. The caller has checked the plan and the LDS
-// sizes (check_metric) and serves the hop-count form itself: metrics do not enter it.
+// The caller serves the hop-count form itself: metrics do not enter it.
 hipError_t whatif_metric_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, const WhatifUnits& un,
                                    const uint32_t* d_sources, uint32_t n_src, uint32_t* d_changed, hipStream_t s,
                                    uint32_t* solved, bool use_link_metric, const WhatifDelta& dl) {
   *solved = 0;
-  if (!n_src || !un.n) return hipSuccess;
-  const size_t units = (size_t)un.n * n_src;
-  if (units > 0xFFFFFFFFull || base_plan.exact || !use_link_metric) return hipErrorInvalidValue;
-  hipError_t err;
-#define OPENR_TRY(x)                   \
-  do {                                 \
-    if ((err = (x)) != hipSuccess) return err; \
-  } while (0)
-  bool base_tin = false;
-  OPENR_TRY(whatif_base_solve(ctx, d, base_plan, d_sources, n_src, s, &base_tin));
-  OPENR_TRY(d.wunit.reserve(units));
-  OPENR_TRY(d.wsrc.reserve(units));
-  OPENR_TRY(d.wcount.reserve(3));
+  if (n_src && un.n && !use_link_metric) return hipErrorInvalidValue;
   MetricPass p{};
-  p.n_events = un.n;
   p.n_edges = un.n_edges;
-  p.n_src = n_src;
-  p.nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
   p.edge_ptr = un.edge_ptr;
   p.edges = un.edges;
   p.metrics = un.metrics;
-  p.sources = d_sources;
-  p.base_dist = d.base_dist.p;
-  p.base_nh = d.base_nh.p;
-  p.base_tight = d.base_tight.p;
-  p.base_tin = base_tin ? d.base_tin.p : nullptr;
-  p.changed = d_changed;
-  p.wunit = d.wunit.p;
-  p.ovf_unit = d.wsrc.p;
-  p.wcount = d.wcount.p;
-  p.ctr = d.work.p + kMetricCtr;
-  p.delta = dl;
-  OPENR_TRY(launch_metric_filter(d.g, p, d.num_cus, s));
-  uint32_t count = 0;
-  OPENR_TRY(hipMemcpyAsync(&count, d.wcount.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  OPENR_TRY(hipStreamSynchronize(s));
-  *solved = count;
-  if (!count) return hipSuccess;
-  OPENR_TRY(launch_metric_repair(d.g, p, count, false, d.num_cus, s));
-  uint32_t over = 0;
-  OPENR_TRY(hipMemcpyAsync(&over, d.wcount.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  OPENR_TRY(hipStreamSynchronize(s));
-  if (over) OPENR_TRY(launch_metric_repair(d.g, p, over, true, d.num_cus, s));
-#undef OPENR_TRY
-  return hipSuccess;
+  return whatif_repair_on_device(ctx, d, base_plan, p, un.n, kMetricCtr, launch_metric_filter, launch_metric_repair,
+                                 d_sources, n_src, d_changed, s, solved, dl);
 }
 
-// Plan and capacity checks of the metric calls, as check_drain: the repair reads base_tight rows.
-int check_metric(const openr_spf_ctx* ctx, uint32_t flags, uint64_t n_events, uint64_t n_sources) {
+// Plan and capacity checks of the drain and metric calls (`word`): the repair reads base_tight
+// rows, which the exact-order kernel's history-dependent pop order does not give a meaning the
+// rule can use. lds(V, dim, S, nb) is the kind's LDS size, dim its L or E (`dim_name`).
+int check_repair_sweep(const openr_spf_ctx* ctx, uint32_t flags, uint64_t n_events, uint64_t n_sources,
+                       const char* word, uint32_t (*lds)(uint32_t, uint32_t, uint32_t, uint32_t), uint32_t slots,
+                       char dim_name, uint32_t dim) {
   if (n_events * n_sources > 0xFFFFFFFFull) return fail(OPENR_SPF_EINVAL, "more than 2^32 - 1 units");
   Plan bp;
   int rc = make_plan(ctx, flags, false, &bp);
   if (rc) return rc;
   if (bp.exact)
-    return fail(OPENR_SPF_ENOTSUP, "metric sweep needs a base plan outside the exact-order kernel (usable metrics in "
-                                   "[1, 2^31-1] under link metric, next-hop sets <= 256 bits)");
+    return fail(OPENR_SPF_ENOTSUP, "%s sweep needs a base plan outside the exact-order kernel (usable metrics in "
+                                   "[1, 2^31-1] under link metric, next-hop sets <= 256 bits)", word);
   const uint32_t nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
-  if (!metric_lds_bytes(ctx->V, ctx->E, std::min(metric_slots(), ctx->V), nb) ||
-      !metric_lds_bytes(ctx->V, ctx->E, ctx->V, nb))
-    return fail(OPENR_SPF_E2BIG, "a metric unit's state does not fit LDS (V=%u, E=%u)", ctx->V, ctx->E);
+  if (!lds(ctx->V, dim, std::min(slots, ctx->V), nb) || !lds(ctx->V, dim, ctx->V, nb))
+    return fail(OPENR_SPF_E2BIG, "a %s unit's state does not fit LDS (V=%u, %c=%u)", word, ctx->V, dim_name, dim);
   return OPENR_SPF_OK;
+}
+
+int check_drain(const openr_spf_ctx* ctx, uint32_t flags, uint64_t n_events, uint64_t n_sources) {
+  return check_repair_sweep(ctx, flags, n_events, n_sources, "drain", drain_lds_bytes, drain_slots(), 'L', ctx->L);
+}
+
+int check_metric(const openr_spf_ctx* ctx, uint32_t flags, uint64_t n_events, uint64_t n_sources) {
+  return check_repair_sweep(ctx, flags, n_events, n_sources, "metric", metric_lds_bytes, metric_slots(), 'E', ctx->E);
 }
 
 hipError_t whatif_units_on_device(openr_spf_ctx* ctx, Device& d, const Plan& bp, const Plan& ip, const WhatifUnits& un,

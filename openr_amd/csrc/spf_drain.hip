@@ -12,8 +12,7 @@
 //     u may expand           iff  u == src  or  (u is not overloaded and u is not in X)
 // dist and nh depend on tight edges only, so a unit none of whose removed edges is tight in
 // the base SPF changes nothing (drain_filter). The others are repaired by one workgroup
-// each (drain_repair), which reads the source's base rows from global memory and keeps only
-// the unit's dirty nodes in LDS slots:
+// each (drain_repair: the slot repair of spf_repair.h under the DrainEvent policy below):
 //   A  = nodes that lose every base-tight in-edge (closure: an A node's own base-tight
 //        out-edges are lost too). Exactly the nodes whose distance grows; every other node
 //        keeps a live tight in-edge whose tail keeps its distance by induction on the base
@@ -24,477 +23,161 @@
 //   D  = closure of the seeds under new-tight out-edges: the only nodes whose next-hop set
 //        can differ (a node outside D has the same tight in-edges from tails whose sets
 //        are unchanged). Next hops of D by a Kahn pass restricted to D.
-// A unit that needs more slots than the launch has is listed for a second launch of the
-// same kernel with one slot per node.
 //
-// Uniformity: barriers sit only in the unit loop and in round loops whose counts are read
-// from LDS at a uniform address between two barriers (uread); loops with per-lane trip
-// counts hold no barrier and no wave collective. The filter's ballot sits outside its
-// lane-dependent loops.
-#include <algorithm>
-
-#include "spf_bfs_common.h"
-#include "spf_kernels.h"
+// Uniformity: the policy's loops (over an event's nodes and links, bitmap words, bits and
+// rows) have per-lane trip counts and hold no barrier and no wave collective.
+#include "spf_repair.h"
 
 namespace openr_spf {
 
 namespace {
 
-constexpr uint32_t kColMask = ~(kEdgeDown | kNodeSink);
-constexpr uint32_t kNoSlot = 0xFFFFu;
-constexpr unsigned long long kInf = ~0ull;
+using repair::in_bm;
+using repair::kColMask;
 
-// One thread per unit, threads in source-major order (t = j * n_events + i), as
-// whatif_set_filter: neighbouring list entries share a source's base rows.
-__global__ __launch_bounds__(256) void drain_filter(const DevGraph g, const DrainPass p) {
-  const uint64_t total = (uint64_t)p.n_events * p.n_src;
-  const uint32_t tw = (g.E + 63u) / 64u;
-  for (uint64_t t0 = (uint64_t)blockIdx.x * 256u; t0 < total; t0 += (uint64_t)gridDim.x * 256u) {
-    const uint64_t t = t0 + threadIdx.x;
-    bool hit = false;
-    uint64_t u = 0;
-    if (t < total) {
-      const uint32_t j = (uint32_t)(t / p.n_events);
-      const uint32_t i = (uint32_t)(t - (uint64_t)j * p.n_events);
-      u = (uint64_t)i * p.n_src + j;
-      p.changed[u] = 0;
-      const uint32_t src = p.sources[j];
-      const uint64_t* trow = p.base_tight + (size_t)j * tw;
-      auto tight = [&](uint32_t e) { return ((trow[e >> 6] >> (e & 63u)) & 1ull) != 0; };
-      const uint32_t b = min(p.node_ptr[i], p.n_nodes);  // a slice never reaches past nodes
-      const uint32_t e = min(max(p.node_ptr[i + 1], b), p.n_nodes);
-      for (uint32_t k = b; k < e && !hit; ++k) {
-        const uint32_t x = p.nodes[k];
-        if (x >= g.V || x == src || g.ovl[x]) continue;
-        const uint2 r = g.row2[x];
-        for (uint32_t ee = r.x; ee < r.y && !hit; ++ee) hit = tight(ee);
-      }
-      if (p.link_ptr) {
-        const uint32_t lb = min(p.link_ptr[i], p.n_links);
-        const uint32_t le = min(max(p.link_ptr[i + 1], lb), p.n_links);
-        for (uint32_t k = lb; k < le && !hit; ++k) {
-          const uint32_t l = p.links[k];
-          if (l >= g.L) continue;
-          const uint2 ee = g.ledge[l];
-          if (ee.x == UINT32_MAX) continue;
-          hit = tight(ee.x) || tight(ee.y);
-        }
+// The repair's LDS with X (V bits) in front of the shared bitmaps and K (L bits) behind them.
+__host__ __device__ constexpr repair::Layout drain_layout(uint32_t V, uint32_t L, uint32_t S, uint32_t nbw) {
+  return repair::layout(V, S, nbw, 4u * ((V + 31u) / 32u), 4u * ((L + 31u) / 32u));
+}
+// the WAN (V = 1000, L = 3000, 2 next-hop bytes) at the default slots: DESIGN.md 5.12
+static_assert(drain_layout(1000, 3000, 128, 1).total == 5904, "drain LDS layout moved");
+
+struct DrainEvent {
+  const DevGraph& g;
+  const DrainPass& p;
+  uint32_t* const xbm;  // X: drained nodes that stop expanding
+  uint32_t* const kbm;  // K: drained links
+  const uint32_t vw, lw;
+  const bool unit_cost;
+  uint32_t i = 0, src = 0;
+
+  static __device__ __forceinline__ repair::Layout layout(const DevGraph& g, uint32_t S, uint32_t nbw) {
+    return drain_layout(g.V, g.L, S, nbw);
+  }
+  __device__ __forceinline__ DrainEvent(const DevGraph& g_, const DrainPass& p_, unsigned char* smem,
+                                        const repair::Layout& lay)
+      : g(g_), p(p_), xbm(reinterpret_cast<uint32_t*>(smem + lay.ev0)),
+        kbm(reinterpret_cast<uint32_t*>(smem + lay.ev1)), vw((g_.V + 31u) / 32u),
+        lw(p_.link_ptr ? (g_.L + 31u) / 32u : 0u), unit_cost(p_.unit_cost != 0) {}
+  __device__ __forceinline__ void begin(uint32_t i_, uint32_t src_) {
+    i = i_;
+    src = src_;
+  }
+  __device__ __forceinline__ bool in_x(uint32_t u) const { return in_bm(xbm, u); }
+  __device__ __forceinline__ bool in_k(uint32_t l) const { return lw && in_bm(kbm, l); }
+
+  __device__ __forceinline__ void reset_word(uint32_t w) const { xbm[w] = 0; }
+  __device__ __forceinline__ void reset(uint32_t tid, uint32_t B) const {
+    for (uint32_t w = tid; w < lw; w += B) kbm[w] = 0;
+  }
+  // X and K as bitmaps (a node or link listed twice sets one bit)
+  __device__ __forceinline__ void build(uint32_t tid, uint32_t B) const {
+    const uint32_t b = min(p.node_ptr[i], p.n_nodes);  // a slice never reaches past nodes
+    const uint32_t e = min(max(p.node_ptr[i + 1], b), p.n_nodes);
+    for (uint32_t t = b + tid; t < e; t += B) {
+      const uint32_t x = p.nodes[t];
+      if (x < g.V && x != src && !g.ovl[x]) atomicOr(&xbm[x >> 5], 1u << (x & 31u));
+    }
+    if (lw) {
+      const uint32_t lb = min(p.link_ptr[i], p.n_links);
+      const uint32_t le = min(max(p.link_ptr[i + 1], lb), p.n_links);
+      for (uint32_t t = lb + tid; t < le; t += B) {
+        const uint32_t l = p.links[t];
+        if (l < g.L && g.ledge[l].x != UINT32_MAX) atomicOr(&kbm[l >> 5], 1u << (l & 31u));
       }
     }
-    const unsigned long long m = __ballot(hit);
-    if (!m) continue;
-    const uint32_t lane = __lane_id();
-    const uint32_t leader = (uint32_t)(__ffsll((long long)m) - 1);
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(p.wcount, (uint32_t)__popcll(m));
-    base = __shfl(base, (int)leader);
-    if (hit) p.wunit[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)u;
   }
-}
-
-// LDS of one workgroup: node-indexed bitmaps and the u16 slot index; everything else is
-// per slot (S of them).
-struct DrainLayout {
-  uint32_t ctl, xbm, abm, sbm, kbm, sidx, dist, node, cnt, nh, alist, q, total;
+  // heads of the base-tight edges the event itself removes, each edge once: the rows of X,
+  // then the edges of K whose tail is not in X
+  template <class Tight, class Fn>
+  __device__ __forceinline__ void walk_event(uint32_t tid, uint32_t B, Tight&& tight, Fn&& fn) const {
+    for (uint32_t w = tid; w < vw; w += B) {
+      for (uint32_t bits = xbm[w]; bits; bits &= bits - 1u) {
+        const uint32_t x = w * 32u + (uint32_t)(__ffs((int)bits) - 1);
+        const uint2 r = g.row2[x];
+        for (uint32_t e = r.x; e < r.y; ++e)
+          if (tight(e)) fn(g.adj[e] & kColMask);
+      }
+    }
+    for (uint32_t w = tid; w < lw; w += B) {
+      for (uint32_t bits = kbm[w]; bits; bits &= bits - 1u) {
+        const uint32_t l = w * 32u + (uint32_t)(__ffs((int)bits) - 1);
+        const uint2 ee = g.ledge[l];
+        const uint32_t c0 = g.adj[ee.x] & kColMask, c1 = g.adj[ee.y] & kColMask;  // ee.x = c1 -> c0
+        if (tight(ee.x) && !in_x(c1)) fn(c0);
+        if (tight(ee.y) && !in_x(c0)) fn(c1);
+      }
+    }
+  }
+  __device__ __forceinline__ bool row_lost(uint32_t u) const { return in_x(u); }  // its row went with the event
+  __device__ __forceinline__ bool out_lost(uint32_t e) const { return in_k(g.lid[e]); }
+  __device__ __forceinline__ bool in_usable(uint32_t link, uint32_t tail) const { return !(in_k(link) || in_x(tail)); }
+  __device__ __forceinline__ bool out_usable(uint32_t e) const { return !in_k(g.lid[e]); }
+  __device__ __forceinline__ unsigned long long w_in(const uint4& rec) const {
+    return unit_cost ? 1ull : (unsigned long long)rec.y;
+  }
+  __device__ __forceinline__ unsigned long long w_out(uint32_t e) const {
+    return unit_cost ? 1ull : (unsigned long long)g.w[e];
+  }
+  __device__ __forceinline__ bool expands(uint32_t u) const { return u == src || (!g.ovl[u] && !in_x(u)); }
 };
 
-__host__ __device__ inline DrainLayout drain_layout(uint32_t V, uint32_t L, uint32_t S, uint32_t nbw) {
-  DrainLayout l;
-  uint32_t off = 0;
-  auto take = [&](uint32_t bytes) {
-    const uint32_t o = off;
-    off += (bytes + 15u) & ~15u;
-    return o;
-  };
-  const uint32_t vw = (V + 31u) / 32u, lw = (L + 31u) / 32u;
-  l.ctl = take(64);
-  l.xbm = take(4u * vw);  // X: drained nodes that stop expanding
-  l.abm = take(4u * vw);  // A
-  l.sbm = take(4u * vw);  // nodes that asked for a slot
-  l.kbm = take(4u * lw);  // K: drained links
-  l.sidx = take(2u * V);  // node -> slot, kNoSlot
-  l.dist = take(8u * S);  // new distance of the slot's node
-  l.node = take(4u * S);
-  l.cnt = take(4u * S);   // live tight in-degree (A closure), then in-degree inside D (Kahn)
-  l.nh = take(4u * S * nbw);
-  l.alist = take(2u * S);  // slots of the A nodes, in joining order
-  l.q = take(2u * S);      // Kahn queue of slots, then the changed slots
-  l.total = off;
-  return l;
+// A unit is hit iff a tight edge sits in a drained node's row or on a drained link.
+__global__ __launch_bounds__(256) void drain_filter(const DevGraph g, const DrainPass p) {
+  const uint32_t tw = (g.E + 63u) / 64u;
+  repair::filter_units(p, [&](uint32_t i, uint32_t j) {
+    bool hit = false;
+    const uint32_t src = p.sources[j];
+    const uint64_t* trow = p.base_tight + (size_t)j * tw;
+    auto tight = [&](uint32_t e) { return ((trow[e >> 6] >> (e & 63u)) & 1ull) != 0; };
+    const uint32_t b = min(p.node_ptr[i], p.n_nodes);  // a slice never reaches past nodes
+    const uint32_t e = min(max(p.node_ptr[i + 1], b), p.n_nodes);
+    for (uint32_t k = b; k < e && !hit; ++k) {
+      const uint32_t x = p.nodes[k];
+      if (x >= g.V || x == src || g.ovl[x]) continue;
+      const uint2 r = g.row2[x];
+      for (uint32_t ee = r.x; ee < r.y && !hit; ++ee) hit = tight(ee);
+    }
+    if (p.link_ptr) {
+      const uint32_t lb = min(p.link_ptr[i], p.n_links);
+      const uint32_t le = min(max(p.link_ptr[i + 1], lb), p.n_links);
+      for (uint32_t k = lb; k < le && !hit; ++k) {
+        const uint32_t l = p.links[k];
+        if (l >= g.L) continue;
+        const uint2 ee = g.ledge[l];
+        if (ee.x == UINT32_MAX) continue;
+        hit = tight(ee.x) || tight(ee.y);
+      }
+    }
+    return hit;
+  });
 }
-
-// ctl words
-enum : uint32_t { kN = 0, kOvf, kNA, kFlag, kQT, kCh, kPoolLo, kPoolHi, kNext };
 
 __global__ __launch_bounds__(256) void drain_repair(const DevGraph g, const DrainPass p, const uint32_t* list,
                                                     uint32_t count, uint32_t S, uint32_t* ovf_list,
                                                     uint32_t* ovf_count) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const uint32_t V = g.V, vw = (V + 31u) / 32u, tw = (g.E + 63u) / 64u;
-  const uint32_t lw = p.link_ptr ? (g.L + 31u) / 32u : 0u;
-  const uint32_t nb = p.nb, nbw = (nb + 3u) / 4u;
-  const DrainLayout lay = drain_layout(V, g.L, S, nbw);
-  uint32_t* const ctl = reinterpret_cast<uint32_t*>(smem + lay.ctl);
-  uint32_t* const xbm = reinterpret_cast<uint32_t*>(smem + lay.xbm);
-  uint32_t* const abm = reinterpret_cast<uint32_t*>(smem + lay.abm);
-  uint32_t* const sbm = reinterpret_cast<uint32_t*>(smem + lay.sbm);
-  uint32_t* const kbm = reinterpret_cast<uint32_t*>(smem + lay.kbm);
-  uint16_t* const sidx = reinterpret_cast<uint16_t*>(smem + lay.sidx);
-  unsigned long long* const dist = reinterpret_cast<unsigned long long*>(smem + lay.dist);
-  uint32_t* const node = reinterpret_cast<uint32_t*>(smem + lay.node);
-  uint32_t* const cnt = reinterpret_cast<uint32_t*>(smem + lay.cnt);
-  uint32_t* const nhw = reinterpret_cast<uint32_t*>(smem + lay.nh);
-  uint16_t* const alist = reinterpret_cast<uint16_t*>(smem + lay.alist);
-  uint16_t* const qq = reinterpret_cast<uint16_t*>(smem + lay.q);
-  const uint32_t tid = threadIdx.x, B = blockDim.x;
-  const bool unit_cost = p.unit_cost != 0;
-  const WhatifDelta& dl = p.delta;
-
-  // a control word every thread reads between two barriers: workgroup-uniform, and the next
-  // write to it comes after the second barrier
-  auto uread = [&](uint32_t i) {
-    __syncthreads();
-    const uint32_t v = ctl[i];
-    __syncthreads();
-    return v;
-  };
-  auto in_bm = [](const uint32_t* bm, uint32_t x) { return ((bm[x >> 5] >> (x & 31u)) & 1u) != 0; };
-
-  for (uint32_t v = tid; v < V; v += B) sidx[v] = (uint16_t)kNoSlot;  // units put it back as they leave
-  if (tid == 0) ctl[kNext] = blockIdx.x;
-  uint32_t k = uread(kNext);
-  while (k < count) {
-    const uint32_t unit = list[k];
-    const uint32_t i = unit / p.n_src, j = unit - i * p.n_src;
-    const uint32_t src = p.sources[j];
-    const unsigned long long* bd = reinterpret_cast<const unsigned long long*>(p.base_dist) + (size_t)j * V;
-    const uint8_t* bh = p.base_nh + (size_t)j * V * nb;
-    const uint64_t* bt = p.base_tight + (size_t)j * tw;
-    const uint16_t* btin = p.base_tin ? p.base_tin + (size_t)j * V : nullptr;
-    auto tight = [&](uint32_t e) { return ((bt[e >> 6] >> (e & 63u)) & 1ull) != 0; };
-    auto in_x = [&](uint32_t u) { return in_bm(xbm, u); };
-    auto in_a = [&](uint32_t u) { return in_bm(abm, u); };
-    auto in_k = [&](uint32_t l) { return lw && in_bm(kbm, l); };
-    auto expands = [&](uint32_t u) { return u == src || (!g.ovl[u] && !in_x(u)); };
-
-    // 0. reset the unit's bitmaps and counters
-    for (uint32_t w = tid; w < vw; w += B) {
-      xbm[w] = 0;
-      abm[w] = 0;
-      sbm[w] = 0;
-    }
-    for (uint32_t w = tid; w < lw; w += B) kbm[w] = 0;
-    if (tid < kNext) ctl[tid] = 0;
-    __syncthreads();
-
-    // 1. X and K as bitmaps (a node or link listed twice sets one bit)
-    {
-      const uint32_t b = min(p.node_ptr[i], p.n_nodes);
-      const uint32_t e = min(max(p.node_ptr[i + 1], b), p.n_nodes);
-      for (uint32_t t = b + tid; t < e; t += B) {
-        const uint32_t x = p.nodes[t];
-        if (x < V && x != src && !g.ovl[x]) atomicOr(&xbm[x >> 5], 1u << (x & 31u));
-      }
-      if (lw) {
-        const uint32_t lb = min(p.link_ptr[i], p.n_links);
-        const uint32_t le = min(max(p.link_ptr[i + 1], lb), p.n_links);
-        for (uint32_t t = lb + tid; t < le; t += B) {
-          const uint32_t l = p.links[t];
-          if (l < g.L && g.ledge[l].x != UINT32_MAX) atomicOr(&kbm[l >> 5], 1u << (l & 31u));
-        }
-      }
-    }
-    __syncthreads();
-
-    // first asker of a node takes a slot for it; the node starts at its base distance
-    auto claim = [&](uint32_t v, bool with_tin) {
-      const uint32_t bit = 1u << (v & 31u);
-      if (atomicOr(&sbm[v >> 5], bit) & bit) return;
-      const uint32_t s = atomicAdd(&ctl[kN], 1u);
-      if (s >= S) {
-        ctl[kOvf] = 1u;
-        return;
-      }
-      uint32_t tin = 0;
-      if (with_tin) {
-        if (btin) {
-          tin = btin[v];
-        } else {
-          const uint2 r = g.row2[v];
-          for (uint32_t e = r.x; e < r.y; ++e) tin += tight(g.erec[e].w) ? 1u : 0u;
-        }
-      }
-      node[s] = v;
-      cnt[s] = tin;
-      dist[s] = bd[v];
-      sidx[v] = (uint16_t)s;
-    };
-    // a removed base-tight edge into v: v joins A with its last one
-    auto lose = [&](uint32_t v) {
-      const uint32_t s = sidx[v];
-      if (s == kNoSlot) return;
-      if (atomicSub(&cnt[s], 1u) != 1u) return;
-      atomicOr(&abm[v >> 5], 1u << (v & 31u));
-      const uint32_t a = atomicAdd(&ctl[kNA], 1u);
-      if (a < S) alist[a] = (uint16_t)s;
-    };
-    // heads of the base-tight edges the event itself removes, each edge once: the rows of X,
-    // then the edges of K whose tail is not in X
-    auto walk_event = [&](auto&& fn) {
-      for (uint32_t w = tid; w < vw; w += B) {
-        for (uint32_t bits = xbm[w]; bits; bits &= bits - 1u) {
-          const uint32_t x = w * 32u + (uint32_t)(__ffs((int)bits) - 1);
-          const uint2 r = g.row2[x];
-          for (uint32_t e = r.x; e < r.y; ++e)
-            if (tight(e)) fn(g.adj[e] & kColMask);
-        }
-      }
-      for (uint32_t w = tid; w < lw; w += B) {
-        for (uint32_t bits = kbm[w]; bits; bits &= bits - 1u) {
-          const uint32_t l = w * 32u + (uint32_t)(__ffs((int)bits) - 1);
-          const uint2 ee = g.ledge[l];
-          const uint32_t c0 = g.adj[ee.x] & kColMask, c1 = g.adj[ee.y] & kColMask;  // ee.x = c1 -> c0
-          if (tight(ee.x) && !in_x(c1)) fn(c0);
-          if (tight(ee.y) && !in_x(c0)) fn(c1);
-        }
-      }
-    };
-    // heads of the base-tight out-edges the A nodes alist[lo, hi) lose and the event left
-    auto walk_a = [&](uint32_t lo, uint32_t hi, auto&& fn) {
-      for (uint32_t t = lo + tid; t < hi; t += B) {
-        const uint32_t u = node[alist[t]];
-        if (in_x(u)) continue;  // its row went with the event
-        const uint2 r = g.row2[u];
-        for (uint32_t e = r.x; e < r.y; ++e)
-          if (tight(e) && !in_k(g.lid[e])) fn(g.adj[e] & kColMask);
-      }
-    };
-
-    // 2. A and the seeds. Each round walks its edges twice: slots first, then the counts
-    walk_event([&](uint32_t v) { claim(v, true); });
-    uint32_t ovf = uread(kOvf);
-    if (!ovf) walk_event(lose);
-    uint32_t lo = 0, hi = uread(kNA);
-    while (!ovf && hi > lo) {
-      walk_a(lo, hi, [&](uint32_t v) { claim(v, true); });
-      ovf = uread(kOvf);
-      if (!ovf) walk_a(lo, hi, lose);
-      lo = hi;
-      hi = min(uread(kNA), S);
-    }
-    const uint32_t na = hi;
-
-    // 3. distances of A: from outside A first, then rounds inside A until nothing improves
-    if (!ovf && na) {
-      for (uint32_t t = tid; t < na; t += B) dist[alist[t]] = kInf;
-      uint32_t again = 1u;
-      for (uint32_t round = 0; again; ++round) {
-        __syncthreads();  // the reset above / the flag read below precede this round's writes
-        for (uint32_t t = tid; t < na; t += B) {
-          const uint32_t s = alist[t], v = node[s];
-          unsigned long long best = dist[s];
-          const uint2 r = g.row2[v];
-          for (uint32_t e = r.x; e < r.y; ++e) {
-            const uint4 rec = g.erec[e];  // in-edge u -> v seen from v's row
-            if (rec.x & kEdgeDown) continue;
-            const uint32_t u = rec.x & kColMask;
-            const bool ua = in_a(u);
-            if (round && !ua) continue;  // tails outside A were taken in round 0
-            if (in_k(rec.z) || in_x(u) || (u != src && (rec.x & kNodeSink))) continue;
-            const unsigned long long du = ua ? dist[sidx[u]] : bd[u];
-            if (du == kInf) continue;
-            const unsigned long long c = du + (unit_cost ? 1ull : (unsigned long long)rec.y);
-            if (c < best) best = c;
-          }
-          if (best < dist[s]) {
-            dist[s] = best;
-            ctl[kFlag] = 1u;
-          }
-        }
-        again = uread(kFlag);
-        if (tid == 0) ctl[kFlag] = 0;
-      }
-    }
-
-    // 4. D: the seeds, then every head of a new-tight edge out of D
-    uint32_t ns = ovf ? 0u : min(uread(kN), S);
-    lo = 0;
-    while (!ovf && ns > lo) {
-      for (uint32_t t = lo + tid; t < ns; t += B) {
-        const uint32_t u = node[t];
-        const unsigned long long du = dist[t];
-        if (du == kInf || !expands(u)) continue;
-        const uint2 r = g.row2[u];
-        for (uint32_t e = r.x; e < r.y; ++e) {
-          const uint32_t a = g.adj[e];
-          if ((a & kEdgeDown) || in_k(g.lid[e])) continue;
-          const uint32_t y = a & kColMask;
-          // only A nodes moved; a slot being filled by another thread is never read here
-          const unsigned long long dy = in_a(y) ? dist[sidx[y]] : bd[y];
-          if (du + (unit_cost ? 1ull : (unsigned long long)g.w[e]) == dy) claim(y, false);
-        }
-      }
-      ovf = uread(kOvf);
-      lo = ns;
-      ns = min(uread(kN), S);
-    }
-
-    // 5. next hops of D: in-degree inside D and the sets entering from outside D, then
-    //    Kahn rounds pushing each finished set over the new-tight edges inside D
-    if (!ovf && ns) {
-      for (uint32_t t = tid; t < ns * nbw; t += B) nhw[t] = 0;
-      __syncthreads();
-      for (uint32_t t = tid; t < ns; t += B) {
-        const uint32_t v = node[t];
-        const unsigned long long dv = dist[t];
-        uint32_t c = 0;
-        if (dv != kInf) {
-          const uint2 r = g.row2[v];
-          for (uint32_t e = r.x; e < r.y; ++e) {
-            const uint4 rec = g.erec[e];
-            if (rec.x & kEdgeDown) continue;
-            const uint32_t u = rec.x & kColMask;
-            if (in_k(rec.z) || in_x(u) || (u != src && (rec.x & kNodeSink))) continue;
-            const uint32_t su = sidx[u];
-            const unsigned long long du = su != kNoSlot ? dist[su] : bd[u];
-            if (du == kInf || du + (unit_cost ? 1ull : (unsigned long long)rec.y) != dv) continue;
-            if (su != kNoSlot) {
-              ++c;
-            } else if (u == src) {
-              const uint32_t bit = g.nbr[rec.w];
-              if (bit < nb * 8u) nhw[t * nbw + (bit >> 5)] |= 1u << (bit & 31u);
-            } else {
-              const uint8_t* h = bh + (size_t)u * nb;
-              for (uint32_t b = 0; b < nb; ++b) nhw[t * nbw + (b >> 2)] |= (uint32_t)h[b] << (8u * (b & 3u));
-            }
-          }
-        }
-        cnt[t] = c;
-        if (c == 0) {
-          const uint32_t at = atomicAdd(&ctl[kQT], 1u);
-          if (at < S) qq[at] = (uint16_t)t;
-        }
-      }
-      lo = 0;
-      hi = min(uread(kQT), S);
-      while (hi > lo) {
-        for (uint32_t t = lo + tid; t < hi; t += B) {
-          const uint32_t s = qq[t], v = node[s];
-          const unsigned long long dv = dist[s];
-          if (dv == kInf || !expands(v)) continue;
-          const uint2 r = g.row2[v];
-          for (uint32_t e = r.x; e < r.y; ++e) {
-            const uint32_t a = g.adj[e];
-            if ((a & kEdgeDown) || in_k(g.lid[e])) continue;
-            const uint32_t sy = sidx[a & kColMask];
-            if (sy == kNoSlot || dv + (unit_cost ? 1ull : (unsigned long long)g.w[e]) != dist[sy]) continue;
-            if (v == src) {
-              const uint32_t bit = g.nbr[e];
-              if (bit < nb * 8u) atomicOr(&nhw[sy * nbw + (bit >> 5)], 1u << (bit & 31u));
-            } else {
-              for (uint32_t w = 0; w < nbw; ++w) {
-                const uint32_t x = nhw[s * nbw + w];
-                if (x) atomicOr(&nhw[sy * nbw + w], x);
-              }
-            }
-            if (atomicSub(&cnt[sy], 1u) == 1u) {
-              const uint32_t at = atomicAdd(&ctl[kQT], 1u);
-              if (at < S) qq[at] = (uint16_t)sy;
-            }
-          }
-        }
-        lo = hi;
-        hi = min(uread(kQT), S);
-      }
-
-      // 6. compare D with the base row; the changed slots, then the unit's delta
-      for (uint32_t t = tid; t < ns; t += B) {
-        const uint32_t v = node[t];
-        bool diff = dist[t] != bd[v];
-        const uint8_t* h = bh + (size_t)v * nb;
-        for (uint32_t b = 0; b < nb && !diff; ++b) diff = ((nhw[t * nbw + (b >> 2)] >> (8u * (b & 3u))) & 0xFFu) != h[b];
-        if (diff) qq[atomicAdd(&ctl[kCh], 1u)] = (uint16_t)t;  // the Kahn queue is done: at most ns entries
-      }
-      const uint32_t total = uread(kCh);
-      if (tid == 0) {
-        p.changed[unit] = total;
-        if (dl.node && total) {  // one pool reservation per unit (WhatifDelta)
-          const unsigned long long b = atomicAdd(dl.used, (unsigned long long)total);
-          dl.off[unit] = dl.base_of(b);
-          ctl[kPoolLo] = (uint32_t)b;
-          ctl[kPoolHi] = (uint32_t)(b >> 32);
-        }
-      }
-      if (dl.node && total) {
-        __syncthreads();
-        const unsigned long long base = ((unsigned long long)ctl[kPoolHi] << 32) | ctl[kPoolLo];
-        for (uint32_t t = tid; t < total; t += B) {
-          const unsigned long long pos = base + t;
-          if (pos >= dl.cap) continue;
-          const uint32_t s = qq[t];
-          dl.node[pos] = node[s];
-          dl.dist[pos] = dist[s];
-          uint8_t* o = dl.nh + (size_t)pos * dl.nhb;
-          for (uint32_t b = 0; b < dl.nhb; ++b)
-            o[b] = b < nb ? (uint8_t)(nhw[s * nbw + (b >> 2)] >> (8u * (b & 3u))) : (uint8_t)0;
-        }
-      }
-    }
-    if (ovf && tid == 0 && ovf_list) ovf_list[atomicAdd(ovf_count, 1u)] = unit;  // the launch with a slot per node
-
-    // the slot index back to empty, the next unit
-    const uint32_t used = min(uread(kN), S);
-    for (uint32_t t = tid; t < used; t += B) sidx[node[t]] = (uint16_t)kNoSlot;
-    if (tid == 0) ctl[kNext] = gridDim.x + atomicAdd(&p.ctr[0], 1u);
-    k = uread(kNext);
-  }
-  bfs::retire_workgroup(p.ctr, nullptr);
+  repair::repair_units<DrainEvent>(g, p, list, count, S, ovf_list, ovf_count);
 }
 
-uint32_t grid_for(uint64_t items, uint32_t per_block, int num_cus) {
-  const uint64_t want = (items + per_block - 1) / per_block;
-  const uint64_t cap = (uint64_t)num_cus * 8u;
-  return (uint32_t)std::max<uint64_t>(1, std::min(want, cap));
-}
+constexpr repair::Kind kDrain = {"drain_filter", "drain_repair", "drain_repair<overflow>", "OPENR_SPF_DRAIN_BLOCK",
+                                 kDrainBlock,    kDrainBlockWide, drain_slots,             &DevGraph::L,
+                                 drain_lds_bytes};
 
 }  // namespace
 
 uint32_t drain_slots() { return bfs::env_u32("OPENR_SPF_DRAIN_SLOTS", kDrainSlots, 1u, 65534u); }
 
 uint32_t drain_lds_bytes(uint32_t V, uint32_t L, uint32_t S, uint32_t nb) {
-  if (S >= kNoSlot) return 0;
-  const uint64_t per_slot = 8u + 4u + 4u + 4u * (uint64_t)((nb + 3u) / 4u) + 2u + 2u;
-  if ((uint64_t)V * 2u + (uint64_t)L / 8u + (uint64_t)S * per_slot > kMaxLds) return 0;  // before the u32 layout sums
-  const uint32_t t = drain_layout(V, L, S, (nb + 3u) / 4u).total;
-  return t <= kMaxLds ? t : 0;
+  return repair::lds_bytes(V, L, S, nb, [&](uint32_t s, uint32_t nbw) { return drain_layout(V, L, s, nbw); });
 }
 
 hipError_t launch_drain_filter(const DevGraph& g, const DrainPass& p, int num_cus, hipStream_t s) {
-  hipError_t err = hipMemsetAsync(p.wcount, 0, 2 * sizeof(uint32_t), s);  // affected units, overflowed units
-  if (err != hipSuccess) return err;
-  const uint64_t total = (uint64_t)p.n_events * p.n_src;
-  if (!total) return hipSuccess;
-  note_launch("drain_filter");
-  hipLaunchKernelGGL(drain_filter, dim3(grid_for(total, 256u, num_cus)), dim3(256), 0, s, g, p);
-  return hipGetLastError();
+  return repair::launch_filter(drain_filter, kDrain, g, p, num_cus, s);
 }
 
 hipError_t launch_drain_repair(const DevGraph& g, const DrainPass& p, uint32_t count, bool rerun, int num_cus,
                                hipStream_t s) {
-  if (!count) return hipSuccess;
-  const uint32_t S = rerun ? g.V : std::min(drain_slots(), g.V);
-  // OPENR_SPF_DRAIN_BLOCK (tuning only): threads per unit of the narrow launch, 64 / 128 / 256
-  uint32_t block = rerun ? kDrainBlockWide : bfs::env_u32("OPENR_SPF_DRAIN_BLOCK", kDrainBlock, 64u, 256u);
-  if (block != 64u && block != 128u && block != 256u) block = kDrainBlock;
-  const uint32_t lds = drain_lds_bytes(g.V, g.L, S, p.nb);
-  if (!lds) return hipErrorInvalidValue;  // the caller checks drain_lds_bytes first
-  hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(drain_repair),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (err != hipSuccess) return err;
-  note_launch(rerun ? "drain_repair<overflow>" : "drain_repair");
-  hipLaunchKernelGGL(drain_repair, dim3(blocks_for(count, lds, num_cus, block)), dim3(block), lds, s, g, p,
-                     rerun ? p.ovf_unit : p.wunit, count, S, rerun ? nullptr : p.ovf_unit, p.wcount + 1);
-  return hipGetLastError();
+  return repair::launch_repair(drain_repair, kDrain, g, p, count, rerun, num_cus, s);
 }
 
 }  // namespace openr_spf

@@ -79,6 +79,8 @@ uint32_t nh_words_for(int mode, uint32_t V);     // LDS dwords of V next-hop set
 bool nh_mode_single(int mode);                  // one node's set lives inside one dword
 // persistent grid: workgroups that fit a CU by LDS (<= 2048 threads) x CUs, <= n
 uint32_t blocks_for(uint32_t n, uint32_t lds, int num_cus, uint32_t block = 256);
+// grid-stride grid: one workgroup per per_block items, at most 8 per CU, at least one
+uint32_t grid_for(uint64_t items, uint32_t per_block, int num_cus);
 
 struct LaunchInfo {
   uint32_t lds_bytes = 0;
@@ -465,17 +467,10 @@ hipError_t launch_wlfa_mark(const WlfaPass& p, int num_cus, hipStream_t s);
 // optr[u] + rank in the pass (any order inside a unit), nothing at or past optr[u + 1].
 hipError_t launch_wlfa(const WlfaPass& p, const WlfaLayout& l, bool emit, hipStream_t s);
 
-// Drain what-if sweep (spf_drain.hip): unit u = i * n_src + j overloads the nodes of event i
-// (nodes[node_ptr[i], node_ptr[i + 1])) and takes its links (links[link_ptr[i], ..), null
-// link_ptr: none) out of service for sources[j]; the rule is in that file's header and at
-// openr_spf_whatif_drain. Slices are clamped to n_nodes / n_links entries and ids out of
-// range are skipped (a malformed device CSR reads nothing past the arrays).
-struct DrainPass {
-  uint32_t n_events, n_nodes, n_links, n_src, nb, unit_cost;
-  const uint32_t* node_ptr;
-  const uint32_t* nodes;
-  const uint32_t* link_ptr;
-  const uint32_t* links;
+// Event what-if sweeps (spf_repair.h): what the drain and the metric pass share. Unit
+// u = i * n_src + j applies event i for sources[j].
+struct RepairPass {
+  uint32_t n_events, n_src, nb;
   const uint32_t* sources;
   const uint64_t* base_dist;   // base rows [n_src][V] (whatif_base_solve)
   const uint8_t* base_nh;      // [n_src][V][nb]
@@ -487,6 +482,19 @@ struct DrainPass {
   uint32_t* wcount;            // [2] affected units, overflowed units
   uint32_t* ctr;               // 2 work counters (zero at rest)
   WhatifDelta delta;           // node == null: counts only
+};
+
+// Drain what-if sweep (spf_drain.hip): unit u = i * n_src + j overloads the nodes of event i
+// (nodes[node_ptr[i], node_ptr[i + 1])) and takes its links (links[link_ptr[i], ..), null
+// link_ptr: none) out of service for sources[j]; the rule is in that file's header and at
+// openr_spf_whatif_drain. Slices are clamped to n_nodes / n_links entries and ids out of
+// range are skipped (a malformed device CSR reads nothing past the arrays).
+struct DrainPass : RepairPass {
+  uint32_t n_nodes, n_links, unit_cost;
+  const uint32_t* node_ptr;
+  const uint32_t* nodes;
+  const uint32_t* link_ptr;
+  const uint32_t* links;
 };
 constexpr uint32_t kDrainCtr = kExactCtr + 2;
 constexpr uint32_t kDrainSlots = 128;      // dirty-node slots of the narrow launch (OPENR_SPF_DRAIN_SLOTS)
@@ -509,22 +517,11 @@ hipError_t launch_drain_repair(const DevGraph& g, const DrainPass& p, uint32_t c
 // metric of edges[k]) for sources[j]; the rule is in that file's header and at
 // openr_spf_whatif_metric. Slices are clamped to n_edges entries; an entry whose id is out
 // of range, whose edge is down or whose metric is not in (current, 2^31 - 1] is skipped.
-struct MetricPass {
-  uint32_t n_events, n_edges, n_src, nb;
+struct MetricPass : RepairPass {
+  uint32_t n_edges;
   const uint32_t* edge_ptr;
   const uint32_t* edges;
   const uint32_t* metrics;
-  const uint32_t* sources;
-  const uint64_t* base_dist;   // base rows [n_src][V] (whatif_base_solve)
-  const uint8_t* base_nh;      // [n_src][V][nb]
-  const uint64_t* base_tight;  // [n_src][ceil(E / 64)]
-  const uint16_t* base_tin;    // nullable [n_src][V] tight in-degrees (rounds plan)
-  uint32_t* changed;           // [units]
-  uint32_t* wunit;             // [units] affected units
-  uint32_t* ovf_unit;          // [units] units that outgrew the narrow launch's slots
-  uint32_t* wcount;            // [2] affected units, overflowed units
-  uint32_t* ctr;               // 2 work counters (zero at rest)
-  WhatifDelta delta;           // node == null: counts only
 };
 constexpr uint32_t kMetricCtr = kDrainCtr + 2;
 constexpr uint32_t kWorkWords = kMetricCtr + 2;  // the counter buffer: the class blocks, then one pair per sweep kernel
@@ -533,15 +530,10 @@ constexpr uint32_t kMetricSlots = 256;      // dirty-node slots of the narrow la
 constexpr uint32_t kMetricBlock = 64;       // threads per unit, narrow launch
 constexpr uint32_t kMetricBlockWide = 256;  // ... and the re-run with a slot per node
 uint32_t metric_slots();
-// LDS of a unit with S slots; 0 when it does not fit kMaxLds (or S outgrows the u16 index).
-// The drain layout without its node and link bitmaps (X, K), plus E bits for the raised edges.
+// As drain_lds_bytes, with E bits for the raised edges in place of the node and link bitmaps.
 uint32_t metric_lds_bytes(uint32_t V, uint32_t E, uint32_t S, uint32_t nb);
-// changed[u] = 0 for every unit; the units with a raised base-tight edge are appended
-// source-major to wunit, wcount[0] of them; wcount[1] = 0.
+// The launchers as the drain's; the filter lists the units with a raised base-tight edge.
 hipError_t launch_metric_filter(const DevGraph& g, const MetricPass& p, int num_cus, hipStream_t s);
-// Repairs wunit[0, count): changed[] and the delta of every listed unit; units past the
-// slots are appended to ovf_unit (wcount[1]). rerun: repairs ovf_unit[0, count) with a slot
-// per node instead (nothing overflows).
 hipError_t launch_metric_repair(const DevGraph& g, const MetricPass& p, uint32_t count, bool rerun, int num_cus,
                                 hipStream_t s);
 

@@ -58,6 +58,12 @@ uint32_t blocks_for(uint32_t n, uint32_t lds, int num_cus, uint32_t block) {
   return (uint32_t)(g ? g : 1);
 }
 
+uint32_t grid_for(uint64_t items, uint32_t per_block, int num_cus) {
+  const uint64_t want = (items + per_block - 1) / per_block;
+  const uint64_t cap = (uint64_t)num_cus * 8u;
+  return (uint32_t)std::max<uint64_t>(1, std::min(want, cap));
+}
+
 bool nh_mode_single(int mode) {
   return mode == kNhNibble || mode == kNhByte || mode == kNhHalf || mode == kNhW1;
 }

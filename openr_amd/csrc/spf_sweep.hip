@@ -1455,12 +1455,6 @@ __global__ __launch_bounds__(256) void iota_u32(uint32_t* p, uint32_t n) {
   for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) p[i] = i;
 }
 
-uint32_t grid_for(uint64_t items, uint32_t per_block, int num_cus) {
-  const uint64_t want = (items + per_block - 1) / per_block;
-  const uint64_t cap = (uint64_t)num_cus * 8u;
-  return (uint32_t)std::max<uint64_t>(1, std::min(want, cap));
-}
-
 }  // namespace
 
 hipError_t launch_whatif_filter(const DevGraph& g, const uint32_t* links, uint32_t n_links, const uint32_t* sources,

@@ -16,6 +16,7 @@ import pytest
 
 from openr_amd import topology as T
 from openr_amd.engine import E2BIG, EINVAL, ENOTSUP, USE_LINK_METRIC, MetricEvents, SpfEngine, SpfError, _p
+import test_gpu_whatif_drain as drain_tests
 from oracle import Oracle
 from test_gpu_routes_resolve import reduce_routes, tables
 from test_gpu_whatif_sets import check_delta, small_graph
@@ -398,6 +399,41 @@ def test_two_device_slots(bfs_family):
             np.testing.assert_array_equal(r[k], want[k])
     finally:
         two.close()
+
+
+# --- 7b. both event sweeps on one engine -------------------------------------------------------------
+def head_of(exp, n_events, n_src):
+    """The first n_events events of an oracle table."""
+    units = n_events * n_src
+    end = int(exp.ptr[units])
+    return dataclasses.replace(exp, changed=exp.changed[:n_events], ptr=exp.ptr[: units + 1], node=exp.node[:end],
+                               dist=exp.dist[:end], nh=exp.nh[:end], same_dist=exp.same_dist[:end])
+
+
+def test_drain_metric_drain_on_one_engine(eng, bfs_family):
+    """The drain and the metric sweep run one repair body and one driver: drain -> metric ->
+    drain on one engine and one graph, each against its module's oracle table; the second
+    drain result is the first, so the counters and the slot index are at rest between sweeps
+    of different kinds."""
+    n = 30
+    g, edge_sets, metric_sets, sources = row_case(0)
+    _, events, drain_sources = drain_tests.single_case(0)
+    assert drain_sources == sources
+    want_d = head_of(drain_tests.oracle_drain(("single", 0), g, events, None, sources), n, len(sources))
+    want_m = head_of(oracle_metric(("row", 0), g, edge_sets, metric_sets, sources), n, len(sources))
+    assert want_d.changed.any() and want_m.changed.any()
+    assert not np.array_equal(want_d.changed, want_m.changed)  # the two kinds answer differently
+    eng.set_graph(g)
+    first = eng.whatif_drain(events[:n], sources)
+    assert "drain_filter" in eng.last_kernels() and "drain_repair" in eng.last_kernels(), eng.last_kernels()
+    check_delta(want_d, *first[:5])
+    got = eng.whatif_metric(edge_sets[:n], metric_sets[:n], sources)
+    assert "metric_filter" in eng.last_kernels() and "metric_repair" in eng.last_kernels(), eng.last_kernels()
+    check_delta(want_m, *got[:5])
+    second = eng.whatif_drain(events[:n], sources)
+    assert "drain_repair" in eng.last_kernels(), eng.last_kernels()
+    for a, b in zip(first, second):
+        np.testing.assert_array_equal(a, b)
 
 
 # --- 8. routes --------------------------------------------------------------------------------------
