@@ -632,8 +632,9 @@ int openr_spf_whatif_drain_routes_device(openr_spf_ctx* ctx, int device_index, c
    slice that is not strictly ascending, a metric below the current one or above 2^31 - 1,
    or n_events * n_sources > 2^32 - 1; OPENR_SPF_ENOTSUP when the base SPF needs the
    exact-order kernel (as openr_spf_whatif_drain); OPENR_SPF_E2BIG when a unit's state does
-   not fit LDS. Not covered: metric decreases, events that mix raises with overload bits or
-   link-down sets, loop-free alternates under a metric event. */
+   not fit LDS. Not covered: events that mix raises with overload bits or link-down sets,
+   loop-free alternates under a metric event. Metric decreases are openr_spf_whatif_restore
+   below. */
 typedef struct {
   uint32_t n_events;
   const uint32_t* edge_ptr;  /* [n_events + 1] */
@@ -673,6 +674,92 @@ int openr_spf_whatif_metric_routes_device(openr_spf_ctx* ctx, int device_index, 
                                           uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
                                           uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes, void* stream,
                                           uint64_t* out_total, uint64_t* out_solved);
+
+/* Restore what-if sweep: what moves when an operator brings routers or links back after
+   maintenance. A restore event i is three lists, each possibly empty: nodes N_i whose overload
+   bit is cleared, links K_i that are put back in service (Link::isUp() becomes true, both
+   directions), and directed CSR edges (the edge ids of openr_spf_patch_graph) with a new,
+   lower metric each. Unit (i, j) is runSpf(sources[j], useLinkMetric) on the graph patched
+   that way, compared with the no-event SPF of sources[j]. Each of these changes nothing:
+     - a node that is not overloaded, a link that is up already, a new metric equal to the
+       current one;
+     - a lowered entry on an edge that is still down after the event;
+     - an entry on a row of a node that still does not expand after the event (overloaded, not
+       in N_i and not the unit's source);
+     - an undrained node that is the unit's own source (the source always expands);
+     - a node or link listed twice counts once; an empty event changes nothing;
+     - next-hop bit positions are those of the unmodified graph (openr_spf_neighbor_map): bits
+       are over distinct columns whatever the link state, so a link coming up renumbers none.
+   changed [n_events][n_sources] = nodes whose distance or next-hop bytes differ (a node that
+   becomes reachable counts). A restore lengthens nothing: no distance grows and no reachable
+   node becomes unreachable. delta (nullable: counts only) is the CSR of
+   openr_spf_whatif_sets_delta over units u = i * n_sources + j: node ids ascending;
+   OPENR_SPF_E2BIG means sum(changed) > cap and nothing else. *out_solved (nullable) = base
+   solves + affected units (units in which a new or cheaper edge reaches its head at or below
+   the head's base distance); it is added to stats.spf_runs. Events are split in contiguous
+   blocks across the context's devices.
+   Without OPENR_SPF_USE_LINK_METRIC the node and link entries act (they add edges) and the
+   metric entries are ignored; unlike openr_spf_whatif_metric the kernels run.
+   Errors: OPENR_SPF_EINVAL for a null or non-ascending node_ptr / link_ptr / edge_ptr (the
+   last two may be NULL), a node >= V, a link >= L, an edge >= E, an event's edge slice that
+   is not strictly ascending, a new metric above the current one (a raise belongs to
+   openr_spf_whatif_metric) or below 1, or n_events * n_sources > 2^32 - 1;
+   OPENR_SPF_ENOTSUP when the base SPF needs the exact-order kernel (as
+   openr_spf_whatif_drain; the hop-count form of such a graph is served), or when under link
+   metric a link of some K_i has a directed edge whose metric after the event lies outside
+   [1, 2^31 - 1] (a down edge may carry any value on a fast plan; restoring it would leave
+   them); OPENR_SPF_E2BIG when a unit's state does not fit LDS. Not covered: loop-free
+   alternates under a restore event, events that mix restores with drains or raises,
+   exact-order base plans. */
+typedef struct {
+  uint32_t n_events;
+  const uint32_t* node_ptr;  /* [n_events + 1] */
+  const uint32_t* nodes;     /* nodes whose overload bit is cleared */
+  const uint32_t* link_ptr;  /* nullable: no links in any event; else [n_events + 1] */
+  const uint32_t* links;     /* links put back in service */
+  const uint32_t* edge_ptr;  /* nullable: no metric entries in any event; else [n_events + 1] */
+  const uint32_t* edges;     /* directed CSR edge ids, strictly ascending inside an event */
+  const uint32_t* metrics;   /* the new metric of edges[k], <= the current one */
+} openr_spf_restore_events_t;
+int openr_spf_whatif_restore(openr_spf_ctx* ctx, const openr_spf_restore_events_t* events, const uint32_t* sources,
+                             uint32_t n_sources, uint32_t flags, uint32_t* changed, openr_spf_whatif_delta_t* delta,
+                             uint64_t* out_solved);
+
+/* Device-buffer form (every buffer device memory), conventions of openr_spf_whatif_drain_device:
+   d_nodes holds n_nodes entries, d_links n_links (d_link_ptr NULL: no links), d_edges and
+   d_metrics n_edges (d_edge_ptr NULL: no metric entries). Nothing is validated: every slice is
+   clamped to its array; an id out of range, an entry whose metric is 0 or not below the
+   current one, and a link whose restored edges would carry a metric outside [1, 2^31 - 1] are
+   skipped. For an edge slice that does not ascend, which of its entries take effect is
+   unspecified; nothing is read out of bounds and every loop terminates. Cap, OPENR_SPF_E2BIG,
+   *out_total and the order of a unit's entries are those of openr_spf_whatif_drain_device.
+   Synchronizes `stream`. */
+int openr_spf_whatif_restore_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
+                                    const uint32_t* d_nodes, const uint32_t* d_link_ptr, const uint32_t* d_links,
+                                    const uint32_t* d_edge_ptr, const uint32_t* d_edges, const uint32_t* d_metrics,
+                                    uint32_t n_events, uint32_t n_nodes, uint32_t n_links, uint32_t n_edges,
+                                    const uint32_t* d_sources, uint32_t n_sources, uint32_t flags, uint32_t* d_changed,
+                                    uint64_t* d_ptr, uint32_t* d_node, uint64_t* d_dist, uint8_t* d_nh, uint64_t cap,
+                                    uint32_t nh_bytes, void* stream, uint64_t* out_total, uint64_t* out_solved);
+
+/* The same sweep resolved to routes over a group table: outputs, route rule and errors of
+   openr_spf_whatif_routes[_device], units and errors of openr_spf_whatif_restore[_device]. A
+   route can turn reachable under a restore event, none turns unreachable. */
+int openr_spf_whatif_restore_routes(openr_spf_ctx* ctx, const openr_spf_restore_events_t* events,
+                                    const uint32_t* sources, uint32_t n_sources, uint32_t flags,
+                                    const openr_spf_groups_t* groups, uint32_t* changed_routes,
+                                    openr_spf_whatif_routes_t* delta, uint64_t* out_solved);
+int openr_spf_whatif_restore_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
+                                           const uint32_t* d_nodes, const uint32_t* d_link_ptr,
+                                           const uint32_t* d_links, const uint32_t* d_edge_ptr,
+                                           const uint32_t* d_edges, const uint32_t* d_metrics, uint32_t n_events,
+                                           uint32_t n_nodes, uint32_t n_links, uint32_t n_edges,
+                                           const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                                           const uint32_t* d_group_ptr, const uint32_t* d_group_nodes,
+                                           uint32_t n_groups, uint32_t n_group_nodes, uint32_t* d_changed_routes,
+                                           uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
+                                           uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes, void* stream,
+                                           uint64_t* out_total, uint64_t* out_solved);
 
 /* LinkState::getKthPaths(src[i], dst[i], 1) and (.., 2) (LinkState.cpp:762-791, with
    traceOnePath :398-419) for a batch of pairs, traced on the device. Per pair, tok1 /

@@ -92,6 +92,7 @@ struct Device {
   DevBuf<uint32_t> wchanged_t;  // grouped repair: results source-major, transposed into the caller's rows
   DevBuf<uint32_t> win_nodes, win_lptr;  // drain sweep, host form: the events' nodes and link_ptr (node_ptr: win_ptr)
   DevBuf<uint32_t> win_edges, win_metrics;  // metric sweep, host form: the events' edges and new metrics (edge_ptr: win_ptr)
+  DevBuf<uint32_t> win_eptr;  // restore sweep, host form: edge_ptr (node_ptr: win_ptr, link_ptr: win_lptr)
   DevBuf<uint16_t> base_tin;  // what-if base SPF: tight in-degree rows (rounds plan)
   size_t wiota_n = 0;  // wiota[0, wiota_n) holds 0, 1, 2, ... (kept across calls)
   // KSP2: base rows, chunk rows, per-chunk ignore slots / sources / pointers, status
@@ -1125,11 +1126,15 @@ struct WhatifUnits {
   const uint32_t* edges = nullptr;
   const uint32_t* metrics = nullptr;
   uint32_t n_edges = 0;  // entries of edges / metrics
+  // restore events: the three CSRs above together (node_ptr set; set_ptr / edge_ptr nullable),
+  // the nodes undrained, the links put back, the metrics lowered
+  bool restore = false;
 };
 
-// Event sweep on one device (openr_spf_whatif_drain / _metric; spf_drain.hip and spf_metric.hip
-// have the unit semantics): base SPF with tight edges -> the filter (source-major list of the
-// units with a hit base-tight edge) -> the count read back (one stream sync) -> the repair,
+// Event sweep on one device (openr_spf_whatif_drain / _metric / _restore; spf_drain.hip,
+// spf_metric.hip and spf_restore.hip have the unit semantics): base SPF with tight edges ->
+// the filter (source-major list of the units the event can change: a hit base-tight edge, or
+// for a restore an improved edge that reaches its head) -> the count read back (one stream sync) -> the repair,
 // one workgroup per listed unit on the base rows -> the units that outgrew its slots (a
 // second 4-byte read) through the same kernel with a slot per node. `p` arrives with its
 // event CSR filled; the common part is filled here. The caller has checked the plan and the
@@ -1213,12 +1218,31 @@ hipError_t whatif_metric_on_device(openr_spf_ctx* ctx, Device& d, const Plan& ba
                                  d_sources, n_src, d_changed, s, solved, dl);
 }
 
+hipError_t whatif_restore_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, const WhatifUnits& un,
+                                    const uint32_t* d_sources, uint32_t n_src, uint32_t* d_changed, hipStream_t s,
+                                    uint32_t* solved, bool use_link_metric, const WhatifDelta& dl) {
+  RestorePass p{};
+  p.n_nodes = un.n_nodes;
+  p.n_links = un.n_set_links;
+  p.n_edges = un.n_edges;
+  p.unit_cost = use_link_metric ? 0u : 1u;
+  p.node_ptr = un.node_ptr;
+  p.nodes = un.nodes;
+  p.link_ptr = un.set_ptr;
+  p.links = un.set_links;
+  p.edge_ptr = un.edge_ptr;
+  p.edges = un.edges;
+  p.metrics = un.metrics;
+  return whatif_repair_on_device(ctx, d, base_plan, p, un.n, kRestoreCtr, launch_restore_filter,
+                                 launch_restore_repair, d_sources, n_src, d_changed, s, solved, dl);
+}
+
 // Plan and capacity checks of the drain and metric calls (`word`): the repair reads base_tight
 // rows, which the exact-order kernel's history-dependent pop order does not give a meaning the
 // rule can use. lds(V, dim, S, nb) is the kind's LDS size, dim its L or E (`dim_name`).
+template <class Lds>
 int check_repair_sweep(const openr_spf_ctx* ctx, uint32_t flags, uint64_t n_events, uint64_t n_sources,
-                       const char* word, uint32_t (*lds)(uint32_t, uint32_t, uint32_t, uint32_t), uint32_t slots,
-                       char dim_name, uint32_t dim) {
+                       const char* word, Lds&& lds, uint32_t slots, char dim_name, uint32_t dim) {
   if (n_events * n_sources > 0xFFFFFFFFull) return fail(OPENR_SPF_EINVAL, "more than 2^32 - 1 units");
   Plan bp;
   int rc = make_plan(ctx, flags, false, &bp);
@@ -1240,9 +1264,19 @@ int check_metric(const openr_spf_ctx* ctx, uint32_t flags, uint64_t n_events, ui
   return check_repair_sweep(ctx, flags, n_events, n_sources, "metric", metric_lds_bytes, metric_slots(), 'E', ctx->E);
 }
 
+int check_restore(const openr_spf_ctx* ctx, uint32_t flags, uint64_t n_events, uint64_t n_sources) {
+  const uint32_t L = ctx->L;
+  return check_repair_sweep(
+      ctx, flags, n_events, n_sources, "restore",
+      [L](uint32_t V, uint32_t E, uint32_t S, uint32_t nb) { return restore_lds_bytes(V, L, E, S, nb); },
+      restore_slots(), 'E', ctx->E);
+}
+
 hipError_t whatif_units_on_device(openr_spf_ctx* ctx, Device& d, const Plan& bp, const Plan& ip, const WhatifUnits& un,
                                   const uint32_t* d_sources, uint32_t n_src, uint32_t* d_changed, hipStream_t s,
                                   uint32_t* solved, bool use_link_metric, const WhatifDelta& dl = WhatifDelta{}) {
+  if (un.restore)
+    return whatif_restore_on_device(ctx, d, bp, un, d_sources, n_src, d_changed, s, solved, use_link_metric, dl);
   if (un.edge_ptr)
     return whatif_metric_on_device(ctx, d, bp, un, d_sources, n_src, d_changed, s, solved, use_link_metric, dl);
   if (un.node_ptr)
@@ -1326,6 +1360,41 @@ int check_whatif_host(const openr_spf_ctx* ctx, const WhatifUnits& hu, const uin
     return fail(OPENR_SPF_EINVAL, "null links, sources or changed");
   for (uint32_t i = 0; i < n_sources; ++i)
     if (sources[i] >= ctx->V) return fail(OPENR_SPF_EINVAL, "source %u out of range (V=%u)", sources[i], ctx->V);
+  if (hu.restore) {  // restore events: node CSR, link CSR (nullable), edge CSR (nullable) with lowers only
+    if (hu.n && !hu.node_ptr) return fail(OPENR_SPF_EINVAL, "null node_ptr");
+    for (uint32_t i = 0; i < hu.n; ++i) {
+      if (hu.node_ptr[i + 1] < hu.node_ptr[i]) return fail(OPENR_SPF_EINVAL, "node_ptr does not ascend at event %u", i);
+      if (hu.set_ptr && hu.set_ptr[i + 1] < hu.set_ptr[i])
+        return fail(OPENR_SPF_EINVAL, "link_ptr does not ascend at event %u", i);
+      if (hu.edge_ptr && hu.edge_ptr[i + 1] < hu.edge_ptr[i])
+        return fail(OPENR_SPF_EINVAL, "edge_ptr does not ascend at event %u", i);
+    }
+    if (!hu.n) return OPENR_SPF_OK;
+    if (hu.node_ptr[hu.n] > hu.node_ptr[0] && !hu.nodes) return fail(OPENR_SPF_EINVAL, "null nodes");
+    if (hu.set_ptr && hu.set_ptr[hu.n] > hu.set_ptr[0] && !hu.set_links) return fail(OPENR_SPF_EINVAL, "null links");
+    if (hu.edge_ptr && hu.edge_ptr[hu.n] > hu.edge_ptr[0] && (!hu.edges || !hu.metrics))
+      return fail(OPENR_SPF_EINVAL, "null edges or metrics");
+    for (uint32_t k = hu.node_ptr[0]; k < hu.node_ptr[hu.n]; ++k)
+      if (hu.nodes[k] >= ctx->V) return fail(OPENR_SPF_EINVAL, "node %u out of range (V=%u)", hu.nodes[k], ctx->V);
+    if (hu.set_ptr)
+      for (uint32_t k = hu.set_ptr[0]; k < hu.set_ptr[hu.n]; ++k)
+        if (hu.set_links[k] >= ctx->L)
+          return fail(OPENR_SPF_EINVAL, "link %u out of range (L=%u)", hu.set_links[k], ctx->L);
+    if (hu.edge_ptr)
+      for (uint32_t i = 0; i < hu.n; ++i)
+        for (uint32_t k = hu.edge_ptr[i]; k < hu.edge_ptr[i + 1]; ++k) {
+          const uint32_t e = hu.edges[k];
+          if (e >= ctx->E) return fail(OPENR_SPF_EINVAL, "edge %u out of range (E=%u)", e, ctx->E);
+          if (k > hu.edge_ptr[i] && e <= hu.edges[k - 1])
+            return fail(OPENR_SPF_EINVAL, "event %u: edge ids are not strictly ascending", i);
+          if (hu.metrics[k] > ctx->metric[e] || hu.metrics[k] < 1u)
+            return fail(OPENR_SPF_EINVAL,
+                        "event %u: metric %u of edge %u is above the current one (%llu: a raise belongs to "
+                        "openr_spf_whatif_metric) or below 1",
+                        i, hu.metrics[k], e, (unsigned long long)ctx->metric[e]);
+        }
+    return OPENR_SPF_OK;
+  }
   if (hu.edge_ptr) {  // metric events: raises only, ids strictly ascending inside an event
     for (uint32_t i = 0; i < hu.n; ++i)
       if (hu.edge_ptr[i + 1] < hu.edge_ptr[i]) return fail(OPENR_SPF_EINVAL, "edge_ptr does not ascend at event %u", i);
@@ -1371,6 +1440,44 @@ int upload_whatif_units(Device& d, const WhatifUnits& hu, uint32_t b, uint32_t m
                         WhatifUnits* un) {
   *un = WhatifUnits{};
   un->n = m;
+  if (hu.restore) {  // restore events: win_ptr / win_nodes, win_lptr / win_links, win_eptr / win_edges / win_metrics
+    // one CSR's block: ptr rebased to the block's slice, the slice of vals (and vals2) behind it
+    auto block = [&](const uint32_t* ptr, const uint32_t* vals, const uint32_t* vals2, DevBuf<uint32_t>& dptr,
+                     DevBuf<uint32_t>& dvals, DevBuf<uint32_t>* dvals2, uint32_t* count) -> int {
+      const uint32_t b0 = ptr[b], e0 = ptr[b + m];
+      rebased->resize(m + 1);
+      for (uint32_t i = 0; i <= m; ++i) (*rebased)[i] = ptr[b + i] - b0;
+      HIP_TRY(dptr.reserve(m + 1));
+      HIP_TRY(dvals.reserve(std::max<uint32_t>(e0 - b0, 1u)));
+      if (dvals2) HIP_TRY(dvals2->reserve(std::max<uint32_t>(e0 - b0, 1u)));
+      HIP_TRY(hipMemcpyAsync(dptr.p, rebased->data(), (m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+      if (e0 > b0) {
+        HIP_TRY(hipMemcpyAsync(dvals.p, vals + b0, (e0 - b0) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+        if (dvals2)
+          HIP_TRY(hipMemcpyAsync(dvals2->p, vals2 + b0, (e0 - b0) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+      }
+      HIP_TRY(hipStreamSynchronize(d.stream));  // `rebased` is reused for the next CSR and the next device's block
+      *count = e0 - b0;
+      return OPENR_SPF_OK;
+    };
+    un->restore = true;
+    int rc = block(hu.node_ptr, hu.nodes, nullptr, d.win_ptr, d.win_nodes, nullptr, &un->n_nodes);
+    if (rc) return rc;
+    un->node_ptr = d.win_ptr.p;
+    un->nodes = d.win_nodes.p;
+    if (hu.set_ptr) {
+      if ((rc = block(hu.set_ptr, hu.set_links, nullptr, d.win_lptr, d.win_links, nullptr, &un->n_set_links))) return rc;
+      un->set_ptr = d.win_lptr.p;
+      un->set_links = d.win_links.p;
+    }
+    if (hu.edge_ptr) {
+      if ((rc = block(hu.edge_ptr, hu.edges, hu.metrics, d.win_eptr, d.win_edges, &d.win_metrics, &un->n_edges))) return rc;
+      un->edge_ptr = d.win_eptr.p;
+      un->edges = d.win_edges.p;
+      un->metrics = d.win_metrics.p;
+    }
+    return OPENR_SPF_OK;
+  }
   if (hu.edge_ptr) {  // metric events: edge CSR in win_ptr / win_edges / win_metrics
     const uint32_t eb = hu.edge_ptr[b], ee = hu.edge_ptr[b + m];
     rebased->resize(m + 1);
@@ -1696,6 +1803,20 @@ int check_metric_events(const openr_spf_ctx* ctx, const openr_spf_metric_events_
 
 WhatifUnits host_metric(const openr_spf_metric_events_t* ev) {
   return metric_units(ev->edge_ptr, ev->edges, ev->metrics, ev->n_events, 0u);
+}
+
+// Restore events as what-if units (host or device memory; the counts: the device form's slice lengths).
+WhatifUnits restore_units(const uint32_t* node_ptr, const uint32_t* nodes, const uint32_t* link_ptr,
+                          const uint32_t* links, const uint32_t* edge_ptr, const uint32_t* edges,
+                          const uint32_t* metrics, uint32_t n_events, uint32_t n_nodes, uint32_t n_links,
+                          uint32_t n_edges) {
+  WhatifUnits un = drain_units(node_ptr, nodes, link_ptr, links, n_events, n_nodes, n_links);
+  un.edge_ptr = n_events ? edge_ptr : nullptr;
+  un.edges = edges;
+  un.metrics = metrics;
+  un.n_edges = n_edges;
+  un.restore = true;
+  return un;
 }
 
 // ---- route-level calls (spf_routes.hip) ---------------------------------------------------
@@ -3767,6 +3888,130 @@ int openr_spf_whatif_metric_routes_device(openr_spf_ctx* ctx, int device_index, 
   rc = whatif_routes_on_device(ctx, d, metric_units(d_edge_ptr, d_edges, d_metrics, n_events, n_edges), d_sources,
                                n_sources, flags, gr, d_changed_routes, d_ptr, d_group, d_metric, d_nh, d_n_best, cap,
                                nh_bytes, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream, &total, &solved);
+  if (out_total) *out_total = total;
+  if (out_solved) *out_solved = solved;
+  return rc;
+}
+
+// Host-form checks of a restore call, in the order EINVAL, the plan's ENOTSUP / E2BIG, then the
+// links whose restored edges would leave the fast plans.
+static int check_restore_host(openr_spf_ctx* ctx, const openr_spf_restore_events_t* ev, const uint32_t* sources,
+                              uint32_t n_sources, uint32_t flags, const uint32_t* changed, WhatifUnits* hu) {
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (!ev) return fail(OPENR_SPF_EINVAL, "null events");
+  if (ev->n_events && !ev->node_ptr) return fail(OPENR_SPF_EINVAL, "null node_ptr");
+  *hu = restore_units(ev->node_ptr, ev->nodes, ev->link_ptr, ev->links, ev->edge_ptr, ev->edges, ev->metrics,
+                      ev->n_events, 0u, 0u, 0u);
+  int rc = check_whatif_host(ctx, *hu, sources, n_sources, changed);
+  if (rc) return rc;
+  if ((rc = check_restore(ctx, flags, ev->n_events, n_sources)) != OPENR_SPF_OK) return rc;
+  if (!(flags & OPENR_SPF_USE_LINK_METRIC) || !hu->set_ptr) return OPENR_SPF_OK;
+  for (uint32_t i = 0; i < hu->n; ++i)
+    for (uint32_t k = hu->set_ptr[i]; k < hu->set_ptr[i + 1]; ++k) {
+      const uint2 de = ctx->ledge[hu->set_links[k]];
+      if (de.x == UINT32_MAX) continue;  // unused id
+      for (const uint32_t e : {de.x, de.y}) {
+        uint64_t m = ctx->metric[e];
+        if (hu->edge_ptr) {  // the event's own entry for e, if any
+          const uint32_t* b = hu->edges + hu->edge_ptr[i];
+          const uint32_t* en = hu->edges + hu->edge_ptr[i + 1];
+          const uint32_t* it = std::lower_bound(b, en, e);
+          if (it != en && *it == e) m = hu->metrics[it - hu->edges];
+        }
+        if (m == 0 || m > 0x7FFFFFFFull)
+          return fail(OPENR_SPF_ENOTSUP,
+                      "event %u: link %u would come up with metric %llu on edge %u, outside [1, 2^31-1] (the base "
+                      "plans after the event would need the exact-order kernel)",
+                      i, hu->set_links[k], (unsigned long long)m, e);
+      }
+    }
+  return OPENR_SPF_OK;
+}
+
+int openr_spf_whatif_restore(openr_spf_ctx* ctx, const openr_spf_restore_events_t* events, const uint32_t* sources,
+                             uint32_t n_sources, uint32_t flags, uint32_t* changed, openr_spf_whatif_delta_t* delta,
+                             uint64_t* out_solved) {
+  clear_launch_trace();
+  WhatifUnits hu;
+  int rc = check_restore_host(ctx, events, sources, n_sources, flags, changed, &hu);
+  if (rc) return rc;
+  if (!delta) return whatif_host(ctx, hu, sources, n_sources, flags, changed, out_solved);
+  return whatif_delta_host(ctx, hu, sources, n_sources, flags, changed, delta, out_solved);
+}
+
+int openr_spf_whatif_restore_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
+                                    const uint32_t* d_nodes, const uint32_t* d_link_ptr, const uint32_t* d_links,
+                                    const uint32_t* d_edge_ptr, const uint32_t* d_edges, const uint32_t* d_metrics,
+                                    uint32_t n_events, uint32_t n_nodes, uint32_t n_links, uint32_t n_edges,
+                                    const uint32_t* d_sources, uint32_t n_sources, uint32_t flags, uint32_t* d_changed,
+                                    uint64_t* d_ptr, uint32_t* d_node, uint64_t* d_dist, uint8_t* d_nh, uint64_t cap,
+                                    uint32_t nh_bytes, void* stream, uint64_t* out_total, uint64_t* out_solved) {
+  clear_launch_trace();
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (n_events && (!d_node_ptr || (n_nodes && !d_nodes) || (d_link_ptr && n_links && !d_links) ||
+                   (d_edge_ptr && n_edges && (!d_edges || !d_metrics))))
+    return fail(OPENR_SPF_EINVAL, "null node_ptr, nodes, links, edges or metrics");
+  int rc = check_restore(ctx, flags, n_events, n_sources);
+  if (rc) return rc;
+  return whatif_delta_device_form(ctx, device_index,
+                                  restore_units(d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges,
+                                                d_metrics, n_events, n_nodes, n_links, n_edges),
+                                  d_sources, n_sources, flags, d_changed, d_ptr, d_node, d_dist, d_nh, cap, nh_bytes,
+                                  stream, out_total, out_solved);
+}
+
+int openr_spf_whatif_restore_routes(openr_spf_ctx* ctx, const openr_spf_restore_events_t* events,
+                                    const uint32_t* sources, uint32_t n_sources, uint32_t flags,
+                                    const openr_spf_groups_t* groups, uint32_t* changed_routes,
+                                    openr_spf_whatif_routes_t* delta, uint64_t* out_solved) {
+  clear_launch_trace();
+  WhatifUnits hu;
+  int rc = check_restore_host(ctx, events, sources, n_sources, flags, changed_routes, &hu);
+  if (rc) return rc;
+  return whatif_routes_host(ctx, hu, sources, n_sources, flags, groups, changed_routes, delta, out_solved);
+}
+
+int openr_spf_whatif_restore_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
+                                           const uint32_t* d_nodes, const uint32_t* d_link_ptr,
+                                           const uint32_t* d_links, const uint32_t* d_edge_ptr,
+                                           const uint32_t* d_edges, const uint32_t* d_metrics, uint32_t n_events,
+                                           uint32_t n_nodes, uint32_t n_links, uint32_t n_edges,
+                                           const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                                           const uint32_t* d_group_ptr, const uint32_t* d_group_nodes,
+                                           uint32_t n_groups, uint32_t n_group_nodes, uint32_t* d_changed_routes,
+                                           uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
+                                           uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes, void* stream,
+                                           uint64_t* out_total, uint64_t* out_solved) {
+  clear_launch_trace();
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (device_index < 0 || device_index >= (int)ctx->devs.size())
+    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+  if ((n_events && (!d_node_ptr || (n_nodes && !d_nodes) || (d_link_ptr && n_links && !d_links) ||
+                    (d_edge_ptr && n_edges && (!d_edges || !d_metrics)))) ||
+      (n_sources && !d_sources) || (n_events && n_sources && !d_changed_routes) || !d_ptr)
+    return fail(OPENR_SPF_EINVAL, "null events, sources, changed_routes or ptr");
+  if ((n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes))
+    return fail(OPENR_SPF_EINVAL, "null group_ptr or group_nodes");
+  if (cap && (!d_group || !d_metric || !d_nh)) return fail(OPENR_SPF_EINVAL, "null route buffer");
+  int rc = check_restore(ctx, flags, n_events, n_sources);
+  if (rc) return rc;
+  Device& d = ctx->devs[device_index];
+  HIP_TRY(hipSetDevice(d.ordinal));
+  DevGroups gr;
+  gr.ptr = d_group_ptr;
+  gr.nodes = d_group_nodes;
+  gr.n = n_groups;
+  gr.m = n_group_nodes;
+  uint64_t total = 0, solved = 0;
+  rc = whatif_routes_on_device(ctx, d,
+                               restore_units(d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics,
+                                             n_events, n_nodes, n_links, n_edges),
+                               d_sources, n_sources, flags, gr, d_changed_routes, d_ptr, d_group, d_metric, d_nh,
+                               d_n_best, cap, nh_bytes, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream,
+                               &total, &solved);
   if (out_total) *out_total = total;
   if (out_solved) *out_solved = solved;
   return rc;

@@ -159,9 +159,10 @@ __global__ __launch_bounds__(256) void drain_repair(const DevGraph g, const Drai
   repair::repair_units<DrainEvent>(g, p, list, count, S, ovf_list, ovf_count);
 }
 
-constexpr repair::Kind kDrain = {"drain_filter", "drain_repair", "drain_repair<overflow>", "OPENR_SPF_DRAIN_BLOCK",
-                                 kDrainBlock,    kDrainBlockWide, drain_slots,             &DevGraph::L,
-                                 drain_lds_bytes};
+constexpr repair::Kind kDrain = {
+    "drain_filter", "drain_repair",  "drain_repair<overflow>", "OPENR_SPF_DRAIN_BLOCK",
+    kDrainBlock,    kDrainBlockWide, drain_slots,
+    [](const DevGraph& g, uint32_t S, uint32_t nb) { return drain_lds_bytes(g.V, g.L, S, nb); }};
 
 }  // namespace
 

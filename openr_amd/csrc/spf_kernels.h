@@ -467,7 +467,7 @@ hipError_t launch_wlfa_mark(const WlfaPass& p, int num_cus, hipStream_t s);
 // optr[u] + rank in the pass (any order inside a unit), nothing at or past optr[u + 1].
 hipError_t launch_wlfa(const WlfaPass& p, const WlfaLayout& l, bool emit, hipStream_t s);
 
-// Event what-if sweeps (spf_repair.h): what the drain and the metric pass share. Unit
+// Event what-if sweeps (spf_repair.h): what the drain, the metric and the restore pass share. Unit
 // u = i * n_src + j applies event i for sources[j].
 struct RepairPass {
   uint32_t n_events, n_src, nb;
@@ -524,7 +524,8 @@ struct MetricPass : RepairPass {
   const uint32_t* metrics;
 };
 constexpr uint32_t kMetricCtr = kDrainCtr + 2;
-constexpr uint32_t kWorkWords = kMetricCtr + 2;  // the counter buffer: the class blocks, then one pair per sweep kernel
+constexpr uint32_t kRestoreCtr = kMetricCtr + 2;
+constexpr uint32_t kWorkWords = kRestoreCtr + 2;  // the counter buffer: the class blocks, then one pair per sweep kernel
 static_assert(kDrainCtr + 2 == kWorkSlots, "the metric sweep's counters follow the last class block");
 constexpr uint32_t kMetricSlots = 256;      // dirty-node slots of the narrow launch (OPENR_SPF_METRIC_SLOTS)
 constexpr uint32_t kMetricBlock = 64;       // threads per unit, narrow launch
@@ -536,6 +537,35 @@ uint32_t metric_lds_bytes(uint32_t V, uint32_t E, uint32_t S, uint32_t nb);
 hipError_t launch_metric_filter(const DevGraph& g, const MetricPass& p, int num_cus, hipStream_t s);
 hipError_t launch_metric_repair(const DevGraph& g, const MetricPass& p, uint32_t count, bool rerun, int num_cus,
                                 hipStream_t s);
+
+// Restore what-if sweep (spf_restore.hip): unit u = i * n_src + j clears the overload bit of
+// event i's nodes, puts its links back in service and lowers the metrics of its directed edges
+// (three CSRs as the drain's and the metric pass's; null link_ptr / edge_ptr: none) for
+// sources[j]; the rule is in that file's header and at openr_spf_whatif_restore. Slices are
+// clamped to n_nodes / n_links / n_edges entries; an id out of range, a node that is not
+// overloaded, a link that is up or whose restored edges would carry a metric outside
+// [1, 2^31 - 1], and an entry whose metric is not in [1, current) are skipped.
+struct RestorePass : RepairPass {
+  uint32_t n_nodes, n_links, n_edges, unit_cost;
+  const uint32_t* node_ptr;
+  const uint32_t* nodes;
+  const uint32_t* link_ptr;
+  const uint32_t* links;
+  const uint32_t* edge_ptr;
+  const uint32_t* edges;
+  const uint32_t* metrics;
+};
+constexpr uint32_t kRestoreSlots = 256;      // dirty-node slots of the narrow launch (OPENR_SPF_RESTORE_SLOTS)
+constexpr uint32_t kRestoreBlock = 64;       // threads per unit, narrow launch
+constexpr uint32_t kRestoreBlockWide = 256;  // ... and the re-run with a slot per node
+uint32_t restore_slots();
+// As drain_lds_bytes, with V bits for the undrained nodes, L for the links and E for the lowered edges.
+uint32_t restore_lds_bytes(uint32_t V, uint32_t L, uint32_t E, uint32_t S, uint32_t nb);
+// The launchers as the drain's; the filter lists the units with an improved edge that reaches
+// its head at or below the head's base distance.
+hipError_t launch_restore_filter(const DevGraph& g, const RestorePass& p, int num_cus, hipStream_t s);
+hipError_t launch_restore_repair(const DevGraph& g, const RestorePass& p, uint32_t count, bool rerun, int num_cus,
+                                 hipStream_t s);
 
 // Incremental mirror updates (spf_update.hip).
 // In-place attribute patch of the device mirror: each record overwrites one element of

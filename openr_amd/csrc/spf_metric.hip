@@ -145,9 +145,10 @@ __global__ __launch_bounds__(256) void metric_repair(const DevGraph g, const Met
   repair::repair_units<MetricEvent>(g, p, list, count, S, ovf_list, ovf_count);
 }
 
-constexpr repair::Kind kMetric = {"metric_filter", "metric_repair",  "metric_repair<overflow>", "OPENR_SPF_METRIC_BLOCK",
-                                  kMetricBlock,    kMetricBlockWide, metric_slots,              &DevGraph::E,
-                                  metric_lds_bytes};
+constexpr repair::Kind kMetric = {
+    "metric_filter", "metric_repair",  "metric_repair<overflow>", "OPENR_SPF_METRIC_BLOCK",
+    kMetricBlock,    kMetricBlockWide, metric_slots,
+    [](const DevGraph& g, uint32_t S, uint32_t nb) { return metric_lds_bytes(g.V, g.E, S, nb); }};
 
 }  // namespace
 

@@ -9,6 +9,8 @@
 // every base-tight in-edge), the seeds, dist(A), D and the Kahn pass over D, as the event
 // files' headers define them. A unit that needs more slots than the launch has is listed for
 // a second launch of the same kernel with one slot per node.
+// The restore sweep (spf_restore.hip) goes the other way, edges appear or get cheaper: it keeps
+// its own repair body and shares filter_units, the layout, the ctl words and the launchers.
 //
 // What an event is enters through a policy struct `Event`, built once per workgroup from
 // (g, p, smem, layout), with plain force-inlined members:
@@ -411,8 +413,7 @@ struct Kind {
   const char* block_env;  // tuning only: threads per unit of the narrow launch, 64 / 128 / 256
   uint32_t block, block_wide;
   uint32_t (*slots)();
-  uint32_t DevGraph::*dim;  // the second argument of lds: L or E
-  uint32_t (*lds)(uint32_t V, uint32_t dim, uint32_t S, uint32_t nb);
+  uint32_t (*lds)(const DevGraph& g, uint32_t S, uint32_t nb);  // LDS of a unit with S slots on g, 0: no fit
 };
 
 template <class Pass>
@@ -435,7 +436,7 @@ hipError_t launch_repair(void (*kernel)(DevGraph, Pass, const uint32_t*, uint32_
   const uint32_t S = rerun ? g.V : std::min(kind.slots(), g.V);
   uint32_t block = rerun ? kind.block_wide : bfs::env_u32(kind.block_env, kind.block, 64u, 256u);
   if (block != 64u && block != 128u && block != 256u) block = kind.block;
-  const uint32_t lds = kind.lds(g.V, g.*kind.dim, S, p.nb);
+  const uint32_t lds = kind.lds(g, S, p.nb);
   if (!lds) return hipErrorInvalidValue;  // the caller checks the LDS size first
   hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

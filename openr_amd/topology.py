@@ -561,6 +561,53 @@ def soft_drain_events(g: CsrGraph, node_sets: Iterable[Iterable[int]], increment
     return metric_events(g, edge_sets, metric_sets)
 
 
+def restore_events(g: CsrGraph, node_sets: Optional[Iterable[Iterable[int]]] = None,
+                   link_sets: Optional[Iterable[Iterable[int]]] = None,
+                   edge_sets: Optional[Iterable[Iterable[int]]] = None,
+                   metric_sets: Optional[Iterable[Iterable[int]]] = None):
+    """Restore events for ``SpfEngine.whatif_restore`` / ``whatif_restore_routes``: per event
+    the nodes whose overload bit is cleared, the links put back in service and the directed CSR
+    edges with their new, lower metric. Any kind may be None (no entry of it in any event);
+    the kinds given must have one entry per event. Nodes and links are validated,
+    de-duplicated and sorted as ``drain_events`` does; edge entries are validated (edge ids
+    in [0, num_dir_edges), new metric in [1, current metric]) and sorted by edge id, and an
+    edge listed twice keeps the lower metric. Returns (node_sets, link_sets, edge_sets,
+    metric_sets), a kind that was None staying None."""
+    if (edge_sets is None) != (metric_sets is None):
+        raise ValueError("edge_sets and metric_sets go together")
+    nodes = prefix_groups(g, node_sets) if node_sets is not None else None
+    links = srlg_sets(g, link_sets) if link_sets is not None else None
+    out_e = out_m = None
+    if edge_sets is not None:
+        edge_sets = [list(x) for x in edge_sets]
+        metric_sets = [list(x) for x in metric_sets]
+        if len(edge_sets) != len(metric_sets):
+            raise ValueError(f"{len(edge_sets)} edge sets but {len(metric_sets)} metric sets")
+        E = g.num_dir_edges
+        out_e, out_m = [], []
+        for k, (edges, metrics) in enumerate(zip(edge_sets, metric_sets)):
+            if len(edges) != len(metrics):
+                raise ValueError(f"event {k}: {len(edges)} edges but {len(metrics)} metrics")
+            best: Dict[int, int] = {}
+            for e, m in zip(edges, metrics):
+                e, m = int(e), int(m)
+                if not 0 <= e < E:
+                    raise ValueError(f"event {k}: edge {e} out of range (E={E})")
+                if m > int(g.metric[e]):
+                    raise ValueError(f"event {k}: metric {m} of edge {e} is above the current one "
+                                     f"({int(g.metric[e])}): a raise is a metric event")
+                if m < 1:
+                    raise ValueError(f"event {k}: metric {m} of edge {e} is below 1")
+                best[e] = min(m, best.get(e, m))
+            ids = sorted(best)
+            out_e.append(ids)
+            out_m.append([best[e] for e in ids])
+    counts = {len(x) for x in (nodes, links, out_e) if x is not None}
+    if len(counts) > 1:
+        raise ValueError(f"the kinds of a restore event list differ in length: {sorted(counts)}")
+    return nodes, links, out_e, out_m
+
+
 def prefix_groups(g: CsrGraph, groups: Iterable[Iterable[int]]) -> List[List[int]]:
     """Caller-given prefix groups (the advertisers of each prefix) as a group table for
     ``SpfEngine.routes`` / ``whatif_routes``: every group validated (node ids in
