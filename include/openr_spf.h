@@ -564,8 +564,9 @@ int openr_spf_whatif_lfa_device(openr_spf_ctx* ctx, int device_index, const uint
    link >= L, or n_events * n_sources > 2^32 - 1; OPENR_SPF_ENOTSUP when the base SPF needs
    the exact-order kernel (zero or wrapped metrics under link metric, next-hop sets wider
    than 256 bits, OPENR_SPF_FORCE_EXACT; the hop-count form of such a graph is served);
-   OPENR_SPF_E2BIG when a unit's state does not fit LDS. Not covered: loop-free alternates
-   under a drain. Metric raises (soft drains) are openr_spf_whatif_metric below. */
+   OPENR_SPF_E2BIG when a unit's state does not fit LDS. Loop-free alternates under a drain
+   are openr_spf_whatif_drain_lfa below. Metric raises (soft drains) are
+   openr_spf_whatif_metric. */
 typedef struct {
   uint32_t n_events;
   const uint32_t* node_ptr;  /* [n_events + 1] */
@@ -607,6 +608,55 @@ int openr_spf_whatif_drain_routes_device(openr_spf_ctx* ctx, int device_index, c
                                          uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes, void* stream,
                                          uint64_t* out_total, uint64_t* out_solved);
 
+/* Loop-free alternates under a drain: which (source, prefix group) pairs move and which stop
+   being protected while routers or links are out for maintenance. Events are those of
+   openr_spf_whatif_drain, groups and outputs those of openr_spf_whatif_lfa (changed,
+   unprotected and lost_backup, each nullable, and the CSR delta), units u = i * n_sources + j.
+   For event i, source j (node s) and group k the entry (metric', nh', alt') is exactly what
+   openr_spf_lfa_routes returns for (s, k) on the graph patched by event i (the graph
+   openr_spf_whatif_drain defines), under the same flags; next-hop bit positions are those of
+   the unmodified graph. An entry changed iff metric', nh' or alt' differs from the no-event
+   entry; unprotected and lost_backup mean what they mean in openr_spf_whatif_lfa.
+     - the reference's LFA loop walks linksFromNode(me) and skips a link only when it is not
+       up (Decision.cpp:1171-1174); it never looks at a neighbour's overload bit, and takes
+       the neighbour's rows from the SPF *from* the neighbour, in which the neighbour expands
+       because it is the source. So a neighbour n of s is tested iff some link s-n has edge_up
+       and is not in K_i; the nodes of N_i change no tested status, and a drained neighbour
+       is tested.
+     - toMe = dist'_n(s); a member d qualifies when dist'_n(d) != UINT64_MAX and dist'_n(d) <
+       metric' + toMe, primes denoting the rows of openr_spf_whatif_drain's unit (i, n), in
+       which n expands as the unit's source. alt' is empty when metric' == UINT64_MAX. Every
+       other rule of openr_spf_lfa_routes holds unchanged.
+   The host form sorts a unit's entries by group id. OPENR_SPF_E2BIG means sum(changed) > cap
+   and nothing else; cap = 0 gives counts and ptr only. *out_solved (nullable) is what
+   openr_spf_whatif_drain reports for the same events over the list "the sources as given,
+   then their up neighbours that are no source, ascending" (the sweep this call runs); it is
+   added to stats.spf_runs. Events are split in contiguous blocks across the context's
+   devices. Errors: events as in openr_spf_whatif_drain (a graph whose repair unit does not
+   fit LDS is OPENR_SPF_ENOTSUP here), groups and metrics as in openr_spf_routes, nh_bytes
+   below the graph's width EINVAL, an exact-order base plan ENOTSUP. Not covered:
+   per-alternate alt_metric entries, perDestination = true, multi-area, and chunking of the
+   sources (as openr_spf_whatif_lfa). */
+int openr_spf_whatif_drain_lfa(openr_spf_ctx* ctx, const openr_spf_drain_events_t* events, const uint32_t* sources,
+                               uint32_t n_sources, uint32_t flags, const openr_spf_groups_t* groups,
+                               uint32_t* changed, uint32_t* unprotected, uint32_t* lost_backup,
+                               openr_spf_whatif_lfa_t* delta, uint64_t* out_solved);
+
+/* Device-buffer form: events as openr_spf_whatif_drain_routes_device, groups and outputs as
+   openr_spf_whatif_lfa_device (d_ptr NULL: counts only; entries in the kernel's order).
+   Nothing is validated: events are clamped and skipped exactly as in
+   openr_spf_whatif_drain_device, groups as in openr_spf_whatif_lfa_device. Synchronizes
+   `stream`. */
+int openr_spf_whatif_drain_lfa_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
+                                      const uint32_t* d_nodes, const uint32_t* d_link_ptr, const uint32_t* d_links,
+                                      uint32_t n_events, uint32_t n_nodes, uint32_t n_links,
+                                      const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                                      const uint32_t* d_group_ptr, const uint32_t* d_group_nodes, uint32_t n_groups,
+                                      uint32_t n_group_nodes, uint32_t* d_changed, uint32_t* d_unprotected,
+                                      uint32_t* d_lost_backup, uint64_t* d_ptr, uint32_t* d_group,
+                                      uint64_t* d_metric, uint8_t* d_nh, uint8_t* d_alt, uint64_t cap,
+                                      uint32_t nh_bytes, void* stream, uint64_t* out_total, uint64_t* out_solved);
+
 /* Metric what-if sweep: what moves when an operator soft-drains a router or a few links by
    raising metrics before maintenance. Traffic is pushed away, but the node stays a transit
    of last resort. A metric event i is a list of directed CSR edges (the edge ids of
@@ -632,9 +682,9 @@ int openr_spf_whatif_drain_routes_device(openr_spf_ctx* ctx, int device_index, c
    slice that is not strictly ascending, a metric below the current one or above 2^31 - 1,
    or n_events * n_sources > 2^32 - 1; OPENR_SPF_ENOTSUP when the base SPF needs the
    exact-order kernel (as openr_spf_whatif_drain); OPENR_SPF_E2BIG when a unit's state does
-   not fit LDS. Not covered: events that mix raises with overload bits or link-down sets,
-   loop-free alternates under a metric event. Metric decreases are openr_spf_whatif_restore
-   below. */
+   not fit LDS. Not covered: events that mix raises with overload bits or link-down sets.
+   Loop-free alternates under a metric event are openr_spf_whatif_metric_lfa below. Metric
+   decreases are openr_spf_whatif_restore. */
 typedef struct {
   uint32_t n_events;
   const uint32_t* edge_ptr;  /* [n_events + 1] */
@@ -675,6 +725,28 @@ int openr_spf_whatif_metric_routes_device(openr_spf_ctx* ctx, int device_index, 
                                           uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes, void* stream,
                                           uint64_t* out_total, uint64_t* out_solved);
 
+/* Loop-free alternates under a metric event: openr_spf_whatif_drain_lfa with the events and
+   the patched graph of openr_spf_whatif_metric. Tested status never changes under a metric
+   event; the rows are those of openr_spf_whatif_metric's unit (i, n); closure, outputs,
+   *out_solved and errors as there, with openr_spf_whatif_metric in place of the drain sweep.
+   Without OPENR_SPF_USE_LINK_METRIC nothing moves: changed and lost_backup are 0, ptr is all
+   zero and unprotected is each source's base count; the base rows of the closure are still
+   solved for that count, no sweep kernel runs, and *out_solved is the number of closure
+   rows. */
+int openr_spf_whatif_metric_lfa(openr_spf_ctx* ctx, const openr_spf_metric_events_t* events, const uint32_t* sources,
+                                uint32_t n_sources, uint32_t flags, const openr_spf_groups_t* groups,
+                                uint32_t* changed, uint32_t* unprotected, uint32_t* lost_backup,
+                                openr_spf_whatif_lfa_t* delta, uint64_t* out_solved);
+int openr_spf_whatif_metric_lfa_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_edge_ptr,
+                                       const uint32_t* d_edges, const uint32_t* d_metrics, uint32_t n_events,
+                                       uint32_t n_edges, const uint32_t* d_sources, uint32_t n_sources,
+                                       uint32_t flags, const uint32_t* d_group_ptr, const uint32_t* d_group_nodes,
+                                       uint32_t n_groups, uint32_t n_group_nodes, uint32_t* d_changed,
+                                       uint32_t* d_unprotected, uint32_t* d_lost_backup, uint64_t* d_ptr,
+                                       uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh, uint8_t* d_alt,
+                                       uint64_t cap, uint32_t nh_bytes, void* stream, uint64_t* out_total,
+                                       uint64_t* out_solved);
+
 /* Restore what-if sweep: what moves when an operator brings routers or links back after
    maintenance. A restore event i is three lists, each possibly empty: nodes N_i whose overload
    bit is cleared, links K_i that are put back in service (Link::isUp() becomes true, both
@@ -708,9 +780,9 @@ int openr_spf_whatif_metric_routes_device(openr_spf_ctx* ctx, int device_index, 
    openr_spf_whatif_drain; the hop-count form of such a graph is served), or when under link
    metric a link of some K_i has a directed edge whose metric after the event lies outside
    [1, 2^31 - 1] (a down edge may carry any value on a fast plan; restoring it would leave
-   them); OPENR_SPF_E2BIG when a unit's state does not fit LDS. Not covered: loop-free
-   alternates under a restore event, events that mix restores with drains or raises,
-   exact-order base plans. */
+   them); OPENR_SPF_E2BIG when a unit's state does not fit LDS. Not covered: events that mix
+   restores with drains or raises, exact-order base plans. Loop-free alternates under a
+   restore event are openr_spf_whatif_restore_lfa below. */
 typedef struct {
   uint32_t n_events;
   const uint32_t* node_ptr;  /* [n_events + 1] */
@@ -760,6 +832,37 @@ int openr_spf_whatif_restore_routes_device(openr_spf_ctx* ctx, int device_index,
                                            uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
                                            uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes, void* stream,
                                            uint64_t* out_total, uint64_t* out_solved);
+
+/* Loop-free alternates under a restore event: openr_spf_whatif_drain_lfa with the events and
+   the patched graph of openr_spf_whatif_restore. A restore can make a neighbour tested that
+   was not, and it can also take a backup away.
+     - a neighbour n of s is tested iff some link s-n has edge_up or is an *effective* link of
+       K_i: down today, and accepted by the restore sweep's own filter. The host form has
+       already refused a link whose restored edges would carry a metric outside [1, 2^31 - 1]
+       under link metric (OPENR_SPF_ENOTSUP); the device form skips such a link, with the
+       same test as openr_spf_whatif_restore_device.
+     - the rows are those of openr_spf_whatif_restore's unit (i, n).
+     - the closure is the sources as given, then *every* distinct neighbour of a source that
+       is no source, whatever the link state, ascending (a neighbour behind a down link can
+       become tested and its base row must be resident); *out_solved is what
+       openr_spf_whatif_restore reports over that list.
+   Outputs, errors and limits as openr_spf_whatif_drain_lfa, with openr_spf_whatif_restore in
+   place of the drain sweep. */
+int openr_spf_whatif_restore_lfa(openr_spf_ctx* ctx, const openr_spf_restore_events_t* events,
+                                 const uint32_t* sources, uint32_t n_sources, uint32_t flags,
+                                 const openr_spf_groups_t* groups, uint32_t* changed, uint32_t* unprotected,
+                                 uint32_t* lost_backup, openr_spf_whatif_lfa_t* delta, uint64_t* out_solved);
+int openr_spf_whatif_restore_lfa_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
+                                        const uint32_t* d_nodes, const uint32_t* d_link_ptr, const uint32_t* d_links,
+                                        const uint32_t* d_edge_ptr, const uint32_t* d_edges,
+                                        const uint32_t* d_metrics, uint32_t n_events, uint32_t n_nodes,
+                                        uint32_t n_links, uint32_t n_edges, const uint32_t* d_sources,
+                                        uint32_t n_sources, uint32_t flags, const uint32_t* d_group_ptr,
+                                        const uint32_t* d_group_nodes, uint32_t n_groups, uint32_t n_group_nodes,
+                                        uint32_t* d_changed, uint32_t* d_unprotected, uint32_t* d_lost_backup,
+                                        uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
+                                        uint8_t* d_alt, uint64_t cap, uint32_t nh_bytes, void* stream,
+                                        uint64_t* out_total, uint64_t* out_solved);
 
 /* LinkState::getKthPaths(src[i], dst[i], 1) and (.., 2) (LinkState.cpp:762-791, with
    traceOnePath :398-419) for a batch of pairs, traced on the device. Per pair, tok1 /

@@ -134,6 +134,10 @@ struct Device {
   DevBuf<uint32_t> wl_clos, wl_bunprot, wl_alist, wl_acount, wl_bm, wl_ochanged, wl_ounprot, wl_olost, wl_ogroup;
   DevBuf<unsigned long long> wl_optr, wl_ometric;
   DevBuf<uint8_t> wl_balt, wl_onh, wl_oalt;
+  // alternates under restore events (spf_elfa.hip): the table of every neighbour with a
+  // closure row, down links included (the base alternates keep lf_trow / lf_ttome)
+  DevBuf<uint32_t> el_trow;
+  DevBuf<unsigned long long> el_ttome;
   // incremental updates: patch records, the last patch's delta edges, refresh work list,
   // host-form refresh rows
   DevBuf<PatchRec> precs;
@@ -2476,9 +2480,15 @@ struct WlfaOut {
 // whatif_routes_on_device), the base routes and base alternates of the sources, the inverse
 // map, the mark pass, the count pass, the scan of the counts, the cap check and the emit
 // pass. OPENR_SPF_E2BIG only ever means sum(changed) > cap. Synchronizes s.
+// fam >= 0 (ElfaFamily; openr_spf_whatif_drain_lfa / _metric_lfa / _restore_lfa): `un` holds
+// events of that family, the node sweep is the family's repair sweep and the passes are those
+// of spf_elfa.hip. A restore widens the closure to every neighbour of a source and gives the
+// pass a table of its own over it; the hop-count form of a metric sweep solves the base rows
+// only (nothing moves: every unit gets its source's base unprotected count).
 int whatif_lfa_on_device(openr_spf_ctx* ctx, Device& d, const WhatifUnits& un, const uint32_t* d_sources,
                          uint32_t n_src, uint32_t flags, const DevGroups& gr, const WlfaOut& out, hipStream_t s,
-                         uint64_t* total, uint64_t* solved_out) {
+                         uint64_t* total, uint64_t* solved_out, int fam = -1) {
+  const bool idle = fam == kElfaMetric && !(flags & OPENR_SPF_USE_LINK_METRIC);
   const uint32_t V = ctx->V, G = gr.n;
   const uint32_t nb = std::max<uint32_t>(1u, (ctx->nh_bits + 7u) / 8u);
   if (out.nhb < nb) return fail(OPENR_SPF_EINVAL, "nh_bytes %u below the graph's next-hop width %u", out.nhb, nb);
@@ -2508,8 +2518,9 @@ int whatif_lfa_on_device(openr_spf_ctx* ctx, Device& d, const WhatifUnits& un, c
   HIP_TRY(d.lf_trow.reserve(E1));
   HIP_TRY(d.lf_ttome.reserve(E1));
   HIP_TRY(d.lf_tfrom.reserve(E1));
-  HIP_TRY(launch_lfa_rows(d.g, d_sources, n_src, d.lf_need.p, d.lf_srcbm.p, d.lf_cnt.p, d.lf_tsum.p, d.lf_wptr.p,
-                          d.lf_list.p, d.lf_rowidx.p, d.num_cus, s));
+  HIP_TRY((fam == kElfaRestore ? launch_elfa_rows : launch_lfa_rows)(d.g, d_sources, n_src, d.lf_need.p, d.lf_srcbm.p,
+                                                                     d.lf_cnt.p, d.lf_tsum.p, d.lf_wptr.p,
+                                                                     d.lf_list.p, d.lf_rowidx.p, d.num_cus, s));
   unsigned long long extra64 = 0;
   HIP_TRY(hipMemcpyAsync(&extra64, d.lf_wptr.p + words, sizeof(extra64), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -2529,7 +2540,17 @@ int whatif_lfa_on_device(openr_spf_ctx* ctx, Device& d, const WhatifUnits& un, c
   if (const char* e = std::getenv("OPENR_SPF_ROUTES_DELTA_CAP"))  // tests: start below the total (the rerun)
     ncap = std::strtoull(e, nullptr, 10);
   uint64_t ntotal = 0;
-  for (int attempt = 0;; ++attempt) {
+  if (idle) {  // the base rows of the closure, no sweep
+    Plan bp;
+    const int rc = make_plan(ctx, flags, false, &bp);
+    if (rc) return rc;
+    bool tin = false;
+    HIP_TRY(whatif_base_solve(ctx, d, bp, d.wl_clos.p, n_rows, s, &tin));
+    *solved_out = n_rows;
+    ctx->stats.spf_runs += n_rows;
+    ctx->stats.batches += 1;
+  }
+  for (int attempt = 0; !idle; ++attempt) {
     HIP_TRY(d.rt_nnode.reserve(std::max<uint64_t>(ncap, 1)));
     HIP_TRY(d.rt_ndist.reserve(std::max<uint64_t>(ncap, 1)));
     HIP_TRY(d.rt_nnh.reserve(std::max<uint64_t>(ncap * nb, 1)));
@@ -2643,8 +2664,40 @@ int whatif_lfa_on_device(openr_spf_ctx* ctx, Device& d, const WhatifUnits& un, c
   p.onh = out.nh;
   p.oalt = out.alt;
   p.g_bm = d.wl_bm.p;
-  HIP_TRY(launch_wlfa_mark(p, d.num_cus, s));
-  HIP_TRY(launch_wlfa(p, lay, false, s));
+  ElfaPass ep{};
+  if (fam >= 0) {
+    if (fam == kElfaRestore) {  // the table over every neighbour with a closure row
+      HIP_TRY(d.el_trow.reserve(E1));
+      HIP_TRY(d.el_ttome.reserve(E1));
+      HIP_TRY(launch_elfa_table(d.g, d_sources, n_src, d.lf_rowidx.p, d.base_dist.p, d.el_trow.p, d.el_ttome.p,
+                                d.num_cus, s));
+      p.trow = d.el_trow.p;
+      p.ttome = d.el_ttome.p;
+      ep.ev.n_nodes = un.n_nodes;
+      ep.ev.n_links = un.n_set_links;
+      ep.ev.n_edges = un.n_edges;
+      ep.ev.unit_cost = (flags & OPENR_SPF_USE_LINK_METRIC) ? 0u : 1u;
+      ep.ev.node_ptr = un.node_ptr;
+      ep.ev.nodes = un.nodes;
+      ep.ev.link_ptr = un.set_ptr;
+      ep.ev.links = un.set_links;
+      ep.ev.edge_ptr = un.edge_ptr;
+      ep.ev.edges = un.edges;
+      ep.ev.metrics = un.metrics;
+    }
+    ep.w = p;
+    ep.idle = idle ? 1u : 0u;
+    HIP_TRY(launch_elfa_mark(d.g, ep, fam, d.num_cus, s));
+    if (idle) {
+      if (out.ptr) HIP_TRY(hipMemsetAsync(out.ptr, 0, (units + 1u) * sizeof(uint64_t), s));
+      HIP_TRY(hipStreamSynchronize(s));
+      return OPENR_SPF_OK;
+    }
+    HIP_TRY(launch_elfa(d.g, ep, lay, fam, false, s));
+  } else {
+    HIP_TRY(launch_wlfa_mark(p, d.num_cus, s));
+    HIP_TRY(launch_wlfa(p, lay, false, s));
+  }
   HIP_TRY(launch_delta_scan(out.changed, units, d.rt_tsum.p, ptr, s));
   unsigned long long tot = 0;
   HIP_TRY(hipMemcpyAsync(&tot, ptr + units, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
@@ -2655,17 +2708,22 @@ int whatif_lfa_on_device(openr_spf_ctx* ctx, Device& d, const WhatifUnits& un, c
     return fail(OPENR_SPF_E2BIG, "%llu entries changed, cap %llu (ptr and the counts are filled, entries are not)", tot,
                 (unsigned long long)out.cap);
   if (tot) {
-    HIP_TRY(launch_wlfa(p, lay, true, s));
+    if (fam >= 0)
+      HIP_TRY(launch_elfa(d.g, ep, lay, fam, true, s));
+    else
+      HIP_TRY(launch_wlfa(p, lay, true, s));
     HIP_TRY(hipStreamSynchronize(s));
   }
   return OPENR_SPF_OK;
 }
 
 // openr_spf_whatif_lfa: sets split in contiguous blocks across the devices, each device's CSR
-// appended to the caller's at the running total, each unit's entries sorted by group id
+// appended to the caller's at the running total, each unit's entries sorted by group id.
+// fam >= 0: `hu` holds events of that ElfaFamily, which the caller has checked as the family's
+// sweep checks them (check_whatif_host below checks their ids again).
 int whatif_lfa_host(openr_spf_ctx* ctx, const WhatifUnits& hu, const uint32_t* sources, uint32_t n_sources,
                     uint32_t flags, const openr_spf_groups_t* g, uint32_t* changed, uint32_t* unprotected,
-                    uint32_t* lost_backup, openr_spf_whatif_lfa_t* delta, uint64_t* out_solved) {
+                    uint32_t* lost_backup, openr_spf_whatif_lfa_t* delta, uint64_t* out_solved, int fam = -1) {
   clear_launch_trace();
   const uint32_t n_sets = hu.n;
   if (out_solved) *out_solved = 0;
@@ -2726,7 +2784,7 @@ int whatif_lfa_host(openr_spf_ctx* ctx, const WhatifUnits& hu, const uint32_t* s
     out.cap = room;
     out.nhb = nhb;
     uint64_t total = 0, solved = 0;
-    rc = whatif_lfa_on_device(ctx, d, un, d.win_src.p, n_sources, flags, gr, out, d.stream, &total, &solved);
+    rc = whatif_lfa_on_device(ctx, d, un, d.win_src.p, n_sources, flags, gr, out, d.stream, &total, &solved, fam);
     if (rc && rc != OPENR_SPF_E2BIG) return rc;
     over |= rc == OPENR_SPF_E2BIG;
     solved_total += solved;
@@ -4203,6 +4261,175 @@ int openr_spf_whatif_lfa_device(openr_spf_ctx* ctx, int device_index, const uint
   if (out_total) *out_total = total;
   if (out_solved) *out_solved = solved;
   return rc;
+}
+
+// ---- loop-free alternates under drain, metric and restore events (spf_elfa.hip) ---------------
+
+// The family's capacity check for a call whose only E2BIG is "sum(changed) > cap": a graph
+// whose repair unit does not fit LDS is not supported by these calls.
+static int event_lfa_check(int rc) {
+  return rc == OPENR_SPF_E2BIG ? OPENR_SPF_ENOTSUP : rc;
+}
+
+// The device forms behind their event arguments (un: events of ElfaFamily fam in device memory).
+static int event_lfa_device(openr_spf_ctx* ctx, int device_index, const WhatifUnits& un, int fam,
+                            const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                            const uint32_t* d_group_ptr, const uint32_t* d_group_nodes, uint32_t n_groups,
+                            uint32_t n_group_nodes, uint32_t* d_changed, uint32_t* d_unprotected,
+                            uint32_t* d_lost_backup, uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric,
+                            uint8_t* d_nh, uint8_t* d_alt, uint64_t cap, uint32_t nh_bytes, void* stream,
+                            uint64_t* out_total, uint64_t* out_solved) {
+  if (device_index < 0 || device_index >= (int)ctx->devs.size())
+    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+  if ((n_sources && !d_sources) || (un.n && n_sources && !d_changed))
+    return fail(OPENR_SPF_EINVAL, "null sources or changed");
+  if ((n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes))
+    return fail(OPENR_SPF_EINVAL, "null group_ptr or group_nodes");
+  if (cap && (!d_ptr || !d_group || !d_metric || !d_nh || !d_alt)) return fail(OPENR_SPF_EINVAL, "null entry buffer");
+  int rc = check_routes_metric(ctx, flags);
+  if (rc) return rc;
+  Device& d = ctx->devs[device_index];
+  HIP_TRY(hipSetDevice(d.ordinal));
+  DevGroups gr;
+  gr.ptr = d_group_ptr;
+  gr.nodes = d_group_nodes;
+  gr.n = n_groups;
+  gr.m = n_group_nodes;
+  WlfaOut out;
+  out.changed = d_changed;
+  out.unprot = d_unprotected;
+  out.lost = d_lost_backup;
+  out.ptr = d_ptr;
+  out.group = d_group;
+  out.metric = d_metric;
+  out.nh = d_nh;
+  out.alt = d_alt;
+  out.cap = cap;
+  out.nhb = nh_bytes;
+  uint64_t total = 0, solved = 0;
+  rc = whatif_lfa_on_device(ctx, d, un, d_sources, n_sources, flags, gr, out,
+                            stream ? reinterpret_cast<hipStream_t>(stream) : d.stream, &total, &solved, fam);
+  if (out_total) *out_total = total;
+  if (out_solved) *out_solved = solved;
+  return rc;
+}
+
+int openr_spf_whatif_drain_lfa(openr_spf_ctx* ctx, const openr_spf_drain_events_t* events, const uint32_t* sources,
+                               uint32_t n_sources, uint32_t flags, const openr_spf_groups_t* groups,
+                               uint32_t* changed, uint32_t* unprotected, uint32_t* lost_backup,
+                               openr_spf_whatif_lfa_t* delta, uint64_t* out_solved) {
+  if (out_solved) *out_solved = 0;
+  int rc = check_drain_events(ctx, events);
+  if (rc) return rc;
+  const WhatifUnits hu = host_drain(events);
+  if ((rc = check_whatif_host(ctx, hu, sources, n_sources, changed)) != OPENR_SPF_OK) return rc;
+  if ((rc = event_lfa_check(check_drain(ctx, flags, events->n_events, n_sources))) != OPENR_SPF_OK) return rc;
+  return whatif_lfa_host(ctx, hu, sources, n_sources, flags, groups, changed, unprotected, lost_backup, delta,
+                         out_solved, kElfaDrain);
+}
+
+int openr_spf_whatif_drain_lfa_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
+                                      const uint32_t* d_nodes, const uint32_t* d_link_ptr, const uint32_t* d_links,
+                                      uint32_t n_events, uint32_t n_nodes, uint32_t n_links,
+                                      const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                                      const uint32_t* d_group_ptr, const uint32_t* d_group_nodes, uint32_t n_groups,
+                                      uint32_t n_group_nodes, uint32_t* d_changed, uint32_t* d_unprotected,
+                                      uint32_t* d_lost_backup, uint64_t* d_ptr, uint32_t* d_group,
+                                      uint64_t* d_metric, uint8_t* d_nh, uint8_t* d_alt, uint64_t cap,
+                                      uint32_t nh_bytes, void* stream, uint64_t* out_total, uint64_t* out_solved) {
+  clear_launch_trace();
+  if (out_total) *out_total = 0;
+  if (out_solved) *out_solved = 0;
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (n_events && (!d_node_ptr || (n_nodes && !d_nodes) || (d_link_ptr && n_links && !d_links)))
+    return fail(OPENR_SPF_EINVAL, "null node_ptr, nodes or links");
+  const int rc = event_lfa_check(check_drain(ctx, flags, n_events, n_sources));
+  if (rc) return rc;
+  return event_lfa_device(ctx, device_index,
+                          drain_units(d_node_ptr, d_nodes, d_link_ptr, d_links, n_events, n_nodes, n_links),
+                          kElfaDrain, d_sources, n_sources, flags, d_group_ptr, d_group_nodes, n_groups,
+                          n_group_nodes, d_changed, d_unprotected, d_lost_backup, d_ptr, d_group, d_metric, d_nh,
+                          d_alt, cap, nh_bytes, stream, out_total, out_solved);
+}
+
+int openr_spf_whatif_metric_lfa(openr_spf_ctx* ctx, const openr_spf_metric_events_t* events, const uint32_t* sources,
+                                uint32_t n_sources, uint32_t flags, const openr_spf_groups_t* groups,
+                                uint32_t* changed, uint32_t* unprotected, uint32_t* lost_backup,
+                                openr_spf_whatif_lfa_t* delta, uint64_t* out_solved) {
+  if (out_solved) *out_solved = 0;
+  int rc = check_metric_events(ctx, events);
+  if (rc) return rc;
+  const WhatifUnits hu = host_metric(events);
+  if ((rc = check_whatif_host(ctx, hu, sources, n_sources, changed)) != OPENR_SPF_OK) return rc;
+  if ((rc = event_lfa_check(check_metric(ctx, flags, events->n_events, n_sources))) != OPENR_SPF_OK) return rc;
+  return whatif_lfa_host(ctx, hu, sources, n_sources, flags, groups, changed, unprotected, lost_backup, delta,
+                         out_solved, kElfaMetric);
+}
+
+int openr_spf_whatif_metric_lfa_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_edge_ptr,
+                                       const uint32_t* d_edges, const uint32_t* d_metrics, uint32_t n_events,
+                                       uint32_t n_edges, const uint32_t* d_sources, uint32_t n_sources,
+                                       uint32_t flags, const uint32_t* d_group_ptr, const uint32_t* d_group_nodes,
+                                       uint32_t n_groups, uint32_t n_group_nodes, uint32_t* d_changed,
+                                       uint32_t* d_unprotected, uint32_t* d_lost_backup, uint64_t* d_ptr,
+                                       uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh, uint8_t* d_alt,
+                                       uint64_t cap, uint32_t nh_bytes, void* stream, uint64_t* out_total,
+                                       uint64_t* out_solved) {
+  clear_launch_trace();
+  if (out_total) *out_total = 0;
+  if (out_solved) *out_solved = 0;
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (n_events && (!d_edge_ptr || (n_edges && (!d_edges || !d_metrics))))
+    return fail(OPENR_SPF_EINVAL, "null edge_ptr, edges or metrics");
+  const int rc = event_lfa_check(check_metric(ctx, flags, n_events, n_sources));
+  if (rc) return rc;
+  return event_lfa_device(ctx, device_index, metric_units(d_edge_ptr, d_edges, d_metrics, n_events, n_edges),
+                          kElfaMetric, d_sources, n_sources, flags, d_group_ptr, d_group_nodes, n_groups,
+                          n_group_nodes, d_changed, d_unprotected, d_lost_backup, d_ptr, d_group, d_metric, d_nh,
+                          d_alt, cap, nh_bytes, stream, out_total, out_solved);
+}
+
+int openr_spf_whatif_restore_lfa(openr_spf_ctx* ctx, const openr_spf_restore_events_t* events,
+                                 const uint32_t* sources, uint32_t n_sources, uint32_t flags,
+                                 const openr_spf_groups_t* groups, uint32_t* changed, uint32_t* unprotected,
+                                 uint32_t* lost_backup, openr_spf_whatif_lfa_t* delta, uint64_t* out_solved) {
+  if (out_solved) *out_solved = 0;
+  WhatifUnits hu;
+  const int rc = event_lfa_check(check_restore_host(ctx, events, sources, n_sources, flags, changed, &hu));
+  if (rc) return rc;
+  return whatif_lfa_host(ctx, hu, sources, n_sources, flags, groups, changed, unprotected, lost_backup, delta,
+                         out_solved, kElfaRestore);
+}
+
+int openr_spf_whatif_restore_lfa_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
+                                        const uint32_t* d_nodes, const uint32_t* d_link_ptr, const uint32_t* d_links,
+                                        const uint32_t* d_edge_ptr, const uint32_t* d_edges,
+                                        const uint32_t* d_metrics, uint32_t n_events, uint32_t n_nodes,
+                                        uint32_t n_links, uint32_t n_edges, const uint32_t* d_sources,
+                                        uint32_t n_sources, uint32_t flags, const uint32_t* d_group_ptr,
+                                        const uint32_t* d_group_nodes, uint32_t n_groups, uint32_t n_group_nodes,
+                                        uint32_t* d_changed, uint32_t* d_unprotected, uint32_t* d_lost_backup,
+                                        uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
+                                        uint8_t* d_alt, uint64_t cap, uint32_t nh_bytes, void* stream,
+                                        uint64_t* out_total, uint64_t* out_solved) {
+  clear_launch_trace();
+  if (out_total) *out_total = 0;
+  if (out_solved) *out_solved = 0;
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (n_events && (!d_node_ptr || (n_nodes && !d_nodes) || (d_link_ptr && n_links && !d_links) ||
+                   (d_edge_ptr && n_edges && (!d_edges || !d_metrics))))
+    return fail(OPENR_SPF_EINVAL, "null node_ptr, nodes, links, edges or metrics");
+  const int rc = event_lfa_check(check_restore(ctx, flags, n_events, n_sources));
+  if (rc) return rc;
+  return event_lfa_device(ctx, device_index,
+                          restore_units(d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics,
+                                        n_events, n_nodes, n_links, n_edges),
+                          kElfaRestore, d_sources, n_sources, flags, d_group_ptr, d_group_nodes, n_groups,
+                          n_group_nodes, d_changed, d_unprotected, d_lost_backup, d_ptr, d_group, d_metric, d_nh,
+                          d_alt, cap, nh_bytes, stream, out_total, out_solved);
 }
 
 int openr_spf_ksp2(openr_spf_ctx* ctx, const uint32_t* src, const uint32_t* dst, uint32_t n_pairs,

@@ -567,6 +567,36 @@ hipError_t launch_restore_filter(const DevGraph& g, const RestorePass& p, int nu
 hipError_t launch_restore_repair(const DevGraph& g, const RestorePass& p, uint32_t count, bool rerun, int num_cus,
                                  hipStream_t s);
 
+// Loop-free alternates under drain, metric and restore events (spf_elfa.hip): the pass of
+// spf_wlfa.hip over the node deltas of an event sweep (events x closure rows). The rule is in
+// that file's header and at openr_spf_whatif_drain_lfa.
+//   w    the pass as spf_wlfa.hip reads it; n_sets = events, set_ptr / set_links = the links
+//        K_i of a drain or restore event (set_ptr null: none), trow / ttome the table of the
+//        neighbours *with a closure row* (restore: every neighbour, launch_elfa_table; else
+//        the base table)
+//   ev   restore only: the event CSRs as the restore sweep takes them (and unit_cost)
+//   idle the hop-count form of a metric sweep: nothing moves, the mark pass lists no unit
+enum ElfaFamily : int { kElfaDrain = 0, kElfaMetric = 1, kElfaRestore = 2 };
+struct ElfaPass {
+  WlfaPass w;
+  RestorePass ev;
+  uint32_t idle;
+};
+// The closure of a restore pass: the sources, then every distinct neighbour of a source that
+// is no source, whatever the state of the links between them (a neighbour behind a down link
+// can become tested). Outputs and scratch as launch_lfa_rows.
+hipError_t launch_elfa_rows(const DevGraph& g, const uint32_t* sources, uint32_t n, uint32_t* need, uint32_t* srcbm,
+                            uint32_t* cnt, unsigned long long* tsum, unsigned long long* wptr, uint32_t* list,
+                            uint32_t* rowidx, int num_cus, hipStream_t s);
+// launch_lfa_table over every edge, down ones included: entry b of source s = (distance row
+// of its b-th distinct neighbour n, base toMe = dist_n(s), UINT64_MAX where n does not reach s).
+hipError_t launch_elfa_table(const DevGraph& g, const uint32_t* sources, uint32_t n, const uint32_t* rowidx,
+                             const uint64_t* dist, uint32_t* trow, unsigned long long* ttome, int num_cus,
+                             hipStream_t s);
+// As launch_wlfa_mark / launch_wlfa for events of family `fam`.
+hipError_t launch_elfa_mark(const DevGraph& g, const ElfaPass& p, int fam, int num_cus, hipStream_t s);
+hipError_t launch_elfa(const DevGraph& g, const ElfaPass& p, const WlfaLayout& l, int fam, bool emit, hipStream_t s);
+
 // Incremental mirror updates (spf_update.hip).
 // In-place attribute patch of the device mirror: each record overwrites one element of
 // one DevGraph array (structure — rows, columns, link ids — never changes).

@@ -62,14 +62,20 @@ EXPORTS = (
     "openr_spf_whatif_drain_device",
     "openr_spf_whatif_drain_routes",
     "openr_spf_whatif_drain_routes_device",
+    "openr_spf_whatif_drain_lfa",
+    "openr_spf_whatif_drain_lfa_device",
     "openr_spf_whatif_metric",
     "openr_spf_whatif_metric_device",
     "openr_spf_whatif_metric_routes",
     "openr_spf_whatif_metric_routes_device",
+    "openr_spf_whatif_metric_lfa",
+    "openr_spf_whatif_metric_lfa_device",
     "openr_spf_whatif_restore",
     "openr_spf_whatif_restore_device",
     "openr_spf_whatif_restore_routes",
     "openr_spf_whatif_restore_routes_device",
+    "openr_spf_whatif_restore_lfa",
+    "openr_spf_whatif_restore_lfa_device",
     "openr_spf_ksp2",
     "openr_spf_ksp2_device",
     "openr_spf_host_alloc",
@@ -302,6 +308,17 @@ def load_library():
                                                          u32, vp, u32, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp,
                                                          ctypes.c_uint64, u32, vp, P(ctypes.c_uint64),
                                                          P(ctypes.c_uint64)]
+    # event arguments as the family's _routes[_device] call, then those of whatif_lfa[_device]
+    lfa_host = [vp, u32, u32, P(SpfGroups), vp, vp, vp, P(WhatifLfa), P(ctypes.c_uint64)]
+    lfa_dev = [vp, u32, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_uint64, u32, vp,
+               P(ctypes.c_uint64), P(ctypes.c_uint64)]
+    l.openr_spf_whatif_drain_lfa.argtypes = [vp, P(DrainEvents)] + lfa_host
+    l.openr_spf_whatif_drain_lfa_device.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, u32, u32, u32] + lfa_dev
+    l.openr_spf_whatif_metric_lfa.argtypes = [vp, P(MetricEvents)] + lfa_host
+    l.openr_spf_whatif_metric_lfa_device.argtypes = [vp, ctypes.c_int, vp, vp, vp, u32, u32] + lfa_dev
+    l.openr_spf_whatif_restore_lfa.argtypes = [vp, P(RestoreEvents)] + lfa_host
+    l.openr_spf_whatif_restore_lfa_device.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32,
+                                                      u32] + lfa_dev
     l.openr_spf_ksp2.argtypes = [vp, vp, vp, u32, u32, vp, vp]
     l.openr_spf_ksp2_device.argtypes = [vp, ctypes.c_int, vp, u32, vp, vp, u32, u32, vp, vp, vp]
     l.openr_spf_host_alloc.argtypes = [ctypes.c_size_t, P(vp)]
@@ -1147,6 +1164,143 @@ class SpfEngine:
         if not (allow_overflow and rc == E2BIG):
             _check(rc)
         return int(total.value), int(solved.value)
+
+    # ---- loop-free alternates under drain, metric and restore events ------------------------
+    def _event_lfa(self, fn, ev, n: int, sources, groups, use_link_metric, nh_bytes, cap, want_counts):
+        """The host call ``fn`` over the events ``ev`` (n of them): the tuple whatif_lfa returns."""
+        gp, gn = _ignore_arrays(groups, len(groups))
+        gs = SpfGroups(len(groups), _p(gp), _p(gn))
+        src = np.ascontiguousarray(sources, dtype=np.uint32)
+        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
+        unprot = np.zeros((n, src.shape[0]), dtype=np.uint32) if want_counts else None
+        lost = np.zeros((n, src.shape[0]), dtype=np.uint32) if want_counts else None
+        solved = ctypes.c_uint64()
+
+        def call(d):
+            return fn(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags, ctypes.byref(gs), _p(changed),
+                      _p(unprot), _p(lost), d, ctypes.byref(solved))
+
+        if cap is None:
+            _check(call(None))
+            cap = int(changed.sum(dtype=np.uint64))
+        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
+        group = np.zeros(max(cap, 1), dtype=np.uint32)
+        metric = np.zeros(max(cap, 1), dtype=np.uint64)
+        nh = np.zeros((max(cap, 1), max(nb, 1)), dtype=np.uint8)
+        alt = np.zeros((max(cap, 1), max(nb, 1)), dtype=np.uint8)
+        d = WhatifLfa(_p(ptr), _p(group), _p(metric), _p(nh), _p(alt), cap, nb)
+        _check(call(ctypes.byref(d)))
+        k = int(ptr[-1])
+        return changed, ptr, group[:k], metric[:k], nh[:k], alt[:k], unprot, lost, int(solved.value)
+
+    def _event_lfa_device(self, fn, event_args, d_sources, n_sources, d_group_ptr, d_group_nodes, n_groups,
+                          n_group_nodes, d_changed, d_unprotected, d_lost_backup, d_ptr, d_group, d_metric, d_nh,
+                          d_alt, cap, nh_bytes, use_link_metric, stream, device_index,
+                          allow_overflow) -> Tuple[int, int]:
+        vp = ctypes.c_void_p
+        total = ctypes.c_uint64()
+        solved = ctypes.c_uint64()
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        rc = fn(self._ctx, device_index, *event_args, vp(d_sources or None), n_sources, flags,
+                vp(d_group_ptr or None), vp(d_group_nodes or None), n_groups, n_group_nodes, vp(d_changed or None),
+                vp(d_unprotected or None), vp(d_lost_backup or None), vp(d_ptr or None), vp(d_group or None),
+                vp(d_metric or None), vp(d_nh or None), vp(d_alt or None), cap, nh_bytes or self.nh_bytes,
+                vp(stream or None), ctypes.byref(total), ctypes.byref(solved))
+        if not (allow_overflow and rc == E2BIG):
+            _check(rc)
+        return int(total.value), int(solved.value)
+
+    def whatif_drain_lfa(self, node_sets: Sequence[Sequence[int]], sources: Sequence[int],
+                         groups: Sequence[Sequence[int]], link_sets: Optional[Sequence[Sequence[int]]] = None,
+                         use_link_metric: bool = True, nh_bytes: Optional[int] = None, cap: Optional[int] = None,
+                         want_counts: bool = True):
+        """Loop-free alternates under drain events (openr_spf_whatif_drain_lfa): the events of
+        whatif_drain, the return tuple of whatif_lfa (changed, ptr, group, metric, nh, alt,
+        unprotected, lost_backup, solved) over units u = i * n_sources + j. cap None: sized from a
+        counts-only call."""
+        ev, keep = self._drain_events(node_sets, link_sets)
+        out = self._event_lfa(self._lib.openr_spf_whatif_drain_lfa, ev, len(node_sets), sources, groups,
+                              use_link_metric, nh_bytes, cap, want_counts)
+        del keep
+        return out
+
+    def whatif_drain_lfa_device(self, d_node_ptr: int, d_nodes: int, d_link_ptr: int, d_links: int, n_events: int,
+                                n_nodes: int, n_links: int, d_sources: int, n_sources: int, d_group_ptr: int,
+                                d_group_nodes: int, n_groups: int, n_group_nodes: int, d_changed: int,
+                                d_unprotected: int = 0, d_lost_backup: int = 0, d_ptr: int = 0, d_group: int = 0,
+                                d_metric: int = 0, d_nh: int = 0, d_alt: int = 0, cap: int = 0, nh_bytes: int = 0,
+                                use_link_metric: bool = True, stream: int = 0, device_index: int = 0,
+                                allow_overflow: bool = False) -> Tuple[int, int]:
+        """Device-pointer form (openr_spf_whatif_drain_lfa_device): (total entries, solved);
+        events as whatif_drain_device, outputs as whatif_lfa_device."""
+        vp = ctypes.c_void_p
+        ev = (vp(d_node_ptr or None), vp(d_nodes or None), vp(d_link_ptr or None), vp(d_links or None), n_events,
+              n_nodes, n_links)
+        return self._event_lfa_device(self._lib.openr_spf_whatif_drain_lfa_device, ev, d_sources, n_sources,
+                                      d_group_ptr, d_group_nodes, n_groups, n_group_nodes, d_changed, d_unprotected,
+                                      d_lost_backup, d_ptr, d_group, d_metric, d_nh, d_alt, cap, nh_bytes,
+                                      use_link_metric, stream, device_index, allow_overflow)
+
+    def whatif_metric_lfa(self, edge_sets: Sequence[Sequence[int]], metric_sets: Sequence[Sequence[int]],
+                          sources: Sequence[int], groups: Sequence[Sequence[int]], use_link_metric: bool = True,
+                          nh_bytes: Optional[int] = None, cap: Optional[int] = None, want_counts: bool = True):
+        """Loop-free alternates under metric events (openr_spf_whatif_metric_lfa): the events of
+        whatif_metric, the return tuple of whatif_lfa. Under hop count nothing moves: changed is
+        all zero and unprotected is each source's base count."""
+        ev, keep = self._metric_events(edge_sets, metric_sets)
+        out = self._event_lfa(self._lib.openr_spf_whatif_metric_lfa, ev, len(edge_sets), sources, groups,
+                              use_link_metric, nh_bytes, cap, want_counts)
+        del keep
+        return out
+
+    def whatif_metric_lfa_device(self, d_edge_ptr: int, d_edges: int, d_metrics: int, n_events: int, n_edges: int,
+                                 d_sources: int, n_sources: int, d_group_ptr: int, d_group_nodes: int,
+                                 n_groups: int, n_group_nodes: int, d_changed: int, d_unprotected: int = 0,
+                                 d_lost_backup: int = 0, d_ptr: int = 0, d_group: int = 0, d_metric: int = 0,
+                                 d_nh: int = 0, d_alt: int = 0, cap: int = 0, nh_bytes: int = 0,
+                                 use_link_metric: bool = True, stream: int = 0, device_index: int = 0,
+                                 allow_overflow: bool = False) -> Tuple[int, int]:
+        """Device-pointer form (openr_spf_whatif_metric_lfa_device): (total entries, solved)."""
+        vp = ctypes.c_void_p
+        ev = (vp(d_edge_ptr or None), vp(d_edges or None), vp(d_metrics or None), n_events, n_edges)
+        return self._event_lfa_device(self._lib.openr_spf_whatif_metric_lfa_device, ev, d_sources, n_sources,
+                                      d_group_ptr, d_group_nodes, n_groups, n_group_nodes, d_changed, d_unprotected,
+                                      d_lost_backup, d_ptr, d_group, d_metric, d_nh, d_alt, cap, nh_bytes,
+                                      use_link_metric, stream, device_index, allow_overflow)
+
+    def whatif_restore_lfa(self, node_sets: Optional[Sequence[Sequence[int]]],
+                           link_sets: Optional[Sequence[Sequence[int]]],
+                           edge_sets: Optional[Sequence[Sequence[int]]],
+                           metric_sets: Optional[Sequence[Sequence[int]]], sources: Sequence[int],
+                           groups: Sequence[Sequence[int]], use_link_metric: bool = True,
+                           nh_bytes: Optional[int] = None, cap: Optional[int] = None, want_counts: bool = True):
+        """Loop-free alternates under restore events (openr_spf_whatif_restore_lfa): the events
+        of whatif_restore, the return tuple of whatif_lfa. A link coming up can make a neighbour
+        tested that was not."""
+        ev, keep, n = self._restore_events(node_sets, link_sets, edge_sets, metric_sets)
+        out = self._event_lfa(self._lib.openr_spf_whatif_restore_lfa, ev, n, sources, groups, use_link_metric,
+                              nh_bytes, cap, want_counts)
+        del keep
+        return out
+
+    def whatif_restore_lfa_device(self, d_node_ptr: int, d_nodes: int, d_link_ptr: int, d_links: int,
+                                  d_edge_ptr: int, d_edges: int, d_metrics: int, n_events: int, n_nodes: int,
+                                  n_links: int, n_edges: int, d_sources: int, n_sources: int, d_group_ptr: int,
+                                  d_group_nodes: int, n_groups: int, n_group_nodes: int, d_changed: int,
+                                  d_unprotected: int = 0, d_lost_backup: int = 0, d_ptr: int = 0, d_group: int = 0,
+                                  d_metric: int = 0, d_nh: int = 0, d_alt: int = 0, cap: int = 0,
+                                  nh_bytes: int = 0, use_link_metric: bool = True, stream: int = 0,
+                                  device_index: int = 0, allow_overflow: bool = False) -> Tuple[int, int]:
+        """Device-pointer form (openr_spf_whatif_restore_lfa_device): (total entries, solved)."""
+        vp = ctypes.c_void_p
+        ev = (vp(d_node_ptr or None), vp(d_nodes or None), vp(d_link_ptr or None), vp(d_links or None),
+              vp(d_edge_ptr or None), vp(d_edges or None), vp(d_metrics or None), n_events, n_nodes, n_links, n_edges)
+        return self._event_lfa_device(self._lib.openr_spf_whatif_restore_lfa_device, ev, d_sources, n_sources,
+                                      d_group_ptr, d_group_nodes, n_groups, n_group_nodes, d_changed, d_unprotected,
+                                      d_lost_backup, d_ptr, d_group, d_metric, d_nh, d_alt, cap, nh_bytes,
+                                      use_link_metric, stream, device_index, allow_overflow)
 
     def ksp2_tokens(self, src: Sequence[int], dst: Sequence[int], tok_cap: int = 256,
                     allow_overflow: bool = False) -> Tuple[np.ndarray, np.ndarray]:
