@@ -214,6 +214,13 @@ int openr_spf_solve_device(openr_spf_ctx* ctx, int device_index,
    its device-form calls raised since the last call (and clears them). */
 int openr_spf_take_status(openr_spf_ctx* ctx, int device_index, uint32_t* out_status);
 
+/* Diagnostics: waits for device `device_index` to go idle, then returns how many rows of
+   its last solve call (openr_spf_solve*, _solve_device) were derived from their neighbours'
+   rows instead of solved (uniform-cost batches that hold those neighbours; OPENR_SPF_DERIVE
+   = 0 / 1 turns the split off / on wherever it is legal). 0 when the call was not split;
+   rows handed to the re-run are counted. */
+int openr_spf_last_derived(openr_spf_ctx* ctx, int device_index, uint32_t* out_derived);
+
 /* Per-link-failure what-if sweep (no reference API: the north-star what-if workload over
    LinkState::runSpf(src, useLinkMetric, {link}), LinkState.cpp:808-882 with the
    linksToIgnore argument getKthPaths uses at :769-779). Unit (i, j) fails links[i] for

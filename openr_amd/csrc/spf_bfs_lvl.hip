@@ -256,6 +256,18 @@ __device__ __forceinline__ void write_rows(const SolveArgs& a, uint32_t sid, uin
   }
 }
 
+// A solved unit of a split batch (SolveArgs::dv) also leaves its u8 level row, 16 bytes per
+// lane and step straight from LDS (`lvl_lds`: the row's LDS byte address, 16-byte aligned, in
+// a region padded to 16 bytes), for nh_derive_kernel to read: plain stores, no `nt`. The
+// stamp tells that kernel the row is this call's; a unit that overflows leaves none.
+__device__ __forceinline__ void leave_level_row(const SolveArgs& a, uint32_t sid, uint32_t V, uint32_t lvl_lds,
+                                                uint32_t t, uint32_t stride) {
+  u32x4* o = reinterpret_cast<u32x4*>(a.dv.rows + (size_t)sid * a.dv.stride);
+  const lds_u128* l = (const lds_u128*)(size_t)lvl_lds;
+  for (uint32_t i = t; i < (V + 15u) / 16u; i += stride) o[i] = l[i];
+  if (t == 0) a.dv.valid[sid] = a.dv.epoch;
+}
+
 // ELLM: 0 = CSR rows only; 1 = the first 4 edges of a row from one 16-byte ELL load,
 // the rest from CSR (G == 1); 2 = ELL only (every row has <= 4 edges, no ignore set,
 // no tight-edge output).
@@ -619,10 +631,12 @@ __host__ __device__ inline LeanLayout lean_layout(uint32_t V, uint32_t nh_words,
 // level resolve to a node whose level is <= L, never tight.
 // WPE: the waves-per-SIMD target the compiler allocates registers for. LDS caps G100 at
 // 10 workgroups of 2 waves per CU (5 per SIMD), and 5 is the default since round 6.
-template <int MODE, int BLOCK, bool PROF, bool DELTA, int WPE>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void bfs_ell_kernel(
-    DevGraph g, SolveArgs a, uint64_t cost, uint32_t ring_cap, uint32_t* ctr, uint32_t* ovf_count,
-    unsigned long long* prof) {
+// DV: the units also leave their level rows (a split batch, SolveArgs::dv): a compile-time
+// variant with a kernel of its own (bfs_ell_rows_kernel), so the plain write-out keeps its
+// code and its `nt` stores.
+template <int MODE, int BLOCK, bool PROF, bool DELTA, bool DV>
+__device__ __forceinline__ void lean_units(const DevGraph& g, const SolveArgs& a, uint64_t cost, uint32_t ring_cap,
+                                           uint32_t* ctr, uint32_t* ovf_count, unsigned long long* prof) {
   using N = Nh<MODE>;
   static_assert(N::kSingle, "single-dword next-hop fields only");
   constexpr uint32_t kBits = 32u / N::kPer;
@@ -902,6 +916,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         if (tid == 0) a.ovf_list[atomicAdd(ovf_count, 1u)] = unit;
       } else {
         write_rows<MODE, uint8_t, BLOCK, false>(a, sid, 0, V, lvl_g, nh_g, cost);
+        if constexpr (DV) leave_level_row(a, sid, V, 32u, tid, (uint32_t)BLOCK);
       }
       if (pf) OPENR_LEAN_STAMP(11, tid);
     }
@@ -918,6 +933,19 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     for (int i = 7; i < 13; ++i) atomicAdd(&prof[4 + i], pacc[i]);
   }
   retire_workgroup(ctr, nullptr);
+}
+
+template <int MODE, int BLOCK, bool PROF, bool DELTA, int WPE>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void bfs_ell_kernel(
+    DevGraph g, SolveArgs a, uint64_t cost, uint32_t ring_cap, uint32_t* ctr, uint32_t* ovf_count,
+    unsigned long long* prof) {
+  lean_units<MODE, BLOCK, PROF, DELTA, false>(g, a, cost, ring_cap, ctr, ovf_count, prof);
+}
+template <int MODE, int BLOCK, bool DELTA, int WPE>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void bfs_ell_rows_kernel(
+    DevGraph g, SolveArgs a, uint64_t cost, uint32_t ring_cap, uint32_t* ctr, uint32_t* ovf_count,
+    unsigned long long* prof) {
+  lean_units<MODE, BLOCK, false, DELTA, true>(g, a, cost, ring_cap, ctr, ovf_count, prof);
 }
 
 // Occupancy first (target workgroups per CU, 8 by default): the full-order u16 variant
@@ -996,8 +1024,10 @@ hipError_t launch_lvl_lean(const DevGraph& g, const SolveArgs& a, uint64_t cost,
   // registers for 5 waves per SIMD, the occupancy LDS allows G100 (10 workgroups of 2 waves
   // per CU): 90 VGPRs, no scratch, 33 SGPR spills; a target of 8 spilled 21 VGPRs to
   // scratch and 50 SGPRs (r06, interleaved A/B: 0.707 vs 0.715 ms median)
+  if (want_prof && a.dv.rows) return hipErrorInvalidValue;  // the profiling variant leaves no level rows
   auto k = want_prof ? (delta ? bfs_ell_kernel<MODE, BLOCK, true, true, 5> : bfs_ell_kernel<MODE, BLOCK, true, false, 5>)
-                     : (delta ? bfs_ell_kernel<MODE, BLOCK, false, true, 5> : bfs_ell_kernel<MODE, BLOCK, false, false, 5>);
+           : a.dv.rows ? (delta ? bfs_ell_rows_kernel<MODE, BLOCK, true, 5> : bfs_ell_rows_kernel<MODE, BLOCK, false, 5>)
+                       : (delta ? bfs_ell_kernel<MODE, BLOCK, false, true, 5> : bfs_ell_kernel<MODE, BLOCK, false, false, 5>);
   hipError_t err =
       hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (err != hipSuccess) return err;
@@ -1106,7 +1136,7 @@ __device__ __forceinline__ void wave_rows_out(const SolveArgs& a, uint32_t sid, 
   }
 }
 
-template <int MODE, uint32_t U>
+template <int MODE, uint32_t U, bool DV>
 __global__ __launch_bounds__(512) void bfs_wave_kernel(DevGraph g, SolveArgs a, uint64_t cost, uint32_t qhalf,
                                                        uint32_t waves, uint32_t* ctr, uint32_t* ovf_count) {
   using N = Nh<MODE>;
@@ -1238,6 +1268,7 @@ __global__ __launch_bounds__(512) void bfs_wave_kernel(DevGraph g, SolveArgs a, 
         if (lane == 0) a.ovf_list[atomicAdd(ovf_count, 1u)] = unit;
       } else {
         wave_rows_out<MODE>(a, sid, V, slot, reinterpret_cast<const uint8_t*>(smem) + slot, nh, cost, lane, 64u);
+        if constexpr (DV) leave_level_row(a, sid, V, slot, lane, 64u);
       }
     }
     uint32_t nx = 0;
@@ -1273,7 +1304,7 @@ hipError_t launch_lvl_wave(const DevGraph& g, const SolveArgs& a, uint64_t cost,
                            uint32_t* ctr, uint32_t* ovf_count, int num_cus, hipStream_t s, LaunchInfo* info) {
   const uint32_t lds = wave_layout(g.V, nh_words_for(MODE, g.V), qhalf, waves).total;
   const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)num_cus, (a.n + waves - 1u) / waves));
-  auto k = bfs_wave_kernel<MODE, 1>;
+  auto k = a.dv.rows ? bfs_wave_kernel<MODE, 1, true> : bfs_wave_kernel<MODE, 1, false>;
   hipError_t err =
       hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (err != hipSuccess) return err;
@@ -1289,23 +1320,47 @@ hipError_t launch_lvl_wave(const DevGraph& g, const SolveArgs& a, uint64_t cost,
   return hipGetLastError();
 }
 
+// Which of the two ELL-only fast passes takes a batch (single-dword next-hop fields, every
+// row within the 4 ELL slots, not sliced): the wave pass (waves != 0, halves of qhalf), else
+// the lean pass, else neither.
+struct FastPass {
+  uint32_t waves = 0, qhalf = 0;
+  bool lean = false;
+};
+FastPass lvl_fast_pass(const DevGraph& g, const SolveArgs& a, int mode, bool has_ign, uint32_t ring_cap, int num_cus) {
+  FastPass f;
+  if (has_ign || a.tight) return f;
+  const uint32_t need1 = std::max<uint32_t>(g.max_deg + 1u, g.est_width1 + g.est_width1 / 4u);
+  // wave pass (graph in LDS) for small batches when the delta rows fit with >= 4 solve
+  // slots per CU (OPENR_SPF_WAVE_QHALF, tests: a smaller half, so wide levels re-run)
+  const uint32_t qforce = env_u32("OPENR_SPF_WAVE_QHALF", 0u, 0u, 65535u);
+  f.qhalf = qforce ? (std::max<uint32_t>(qforce, g.max_deg + 1u) + 15u) & ~15u
+                   : (std::max<uint32_t>(64u, need1) + 15u) & ~15u;
+  f.waves = wave_pass_waves(g, mode, f.qhalf, a.n, num_cus);
+  if (f.waves || !ring_cap) return f;
+  // lean pass: its queue halves must hold the widest sampled level (else the generic ring)
+  // (OPENR_SPF_LEAN_FORCE=1, tests: also when the halves are too small, so wide levels
+  // take the overflow -> u16 re-run path)
+  f.lean = ring_cap / 2u >= need1 || env_u32("OPENR_SPF_LEAN_FORCE", 0u, 0u, 1u) != 0u;
+  return f;
+}
+
 template <int MODE, int BLOCK, int ELLM, bool SLICED>
 hipError_t launch_lvl_mode(const DevGraph& g, const SolveArgs& a, uint64_t cost, uint32_t glog, bool has_ign,
                            uint32_t ring_cap, int num_cus, hipStream_t s, LaunchInfo* info) {
   // Counter block of the class: [0,1] first launch, [2,3] re-run launch, [4] listed units.
   uint32_t* blk = class_counters(a);
   hipError_t err;
+  FastPass fp;
+  if constexpr (ELLM == 2 && !SLICED && Nh<MODE>::kSingle) fp = lvl_fast_pass(g, a, MODE, has_ign, ring_cap, num_cus);
+  // a split batch: only the fast passes leave level rows (bfs_lvl_fast_pass tells the caller)
+  if (a.dv.rows && !fp.waves && !fp.lean) return hipErrorInvalidValue;
   if constexpr (ELLM == 2 && !SLICED && Nh<MODE>::kSingle) {
-    const uint32_t need1 = std::max<uint32_t>(g.max_deg + 1u, g.est_width1 + g.est_width1 / 4u);
-    // wave pass (graph in LDS) for small batches when the delta rows fit with >= 4 solve
-    // slots per CU (OPENR_SPF_WAVE_QHALF, tests: a smaller half, so wide levels re-run)
-    const uint32_t qforce = env_u32("OPENR_SPF_WAVE_QHALF", 0u, 0u, 65535u);
-    const uint32_t qhalf = qforce ? (std::max<uint32_t>(qforce, g.max_deg + 1u) + 15u) & ~15u
-                                  : (std::max<uint32_t>(64u, need1) + 15u) & ~15u;
-    const uint32_t waves = (!has_ign && !a.tight) ? wave_pass_waves(g, MODE, qhalf, a.n, num_cus) : 0u;
-    if (waves) {
-      err = launch_lvl_wave<MODE>(g, a, cost, qhalf, waves, blk, blk + 4, num_cus, s, info);
-      if (err != hipSuccess || (g.V <= qhalf && g.V <= 254u)) return err;  // nothing can overflow
+    if (fp.waves) {
+      err = launch_lvl_wave<MODE>(g, a, cost, fp.qhalf, fp.waves, blk, blk + 4, num_cus, s, info);
+      // derived rows from the level rows just left; its overflows join the re-run list
+      if (err == hipSuccess && a.dv.rows) err = launch_nh_derive(g, a, cost, blk + 4, num_cus, s);
+      if (err != hipSuccess || (g.V <= fp.qhalf && g.V <= 254u)) return err;  // nothing can overflow
       return launch_lvl_variant<MODE, 256, uint16_t, false, ELLM, SLICED>(g, a, cost, glog, has_ign, g.V, true,
                                                                           blk + 2, blk + 4, num_cus, s, info);
     }
@@ -1314,17 +1369,13 @@ hipError_t launch_lvl_mode(const DevGraph& g, const SolveArgs& a, uint64_t cost,
     return launch_lvl_variant<MODE, BLOCK, uint16_t, false, ELLM, SLICED>(g, a, cost, glog, has_ign, g.V, false, blk,
                                                                           blk + 4, num_cus, s, info);
   if constexpr (ELLM == 2 && !SLICED && Nh<MODE>::kSingle) {
-    // lean pass: its queue halves must hold the widest sampled level (else the generic ring)
-    const uint32_t need1 = std::max<uint32_t>(g.max_deg + 1u, g.est_width1 + g.est_width1 / 4u);
-    // (OPENR_SPF_LEAN_FORCE=1, tests: also when the halves are too small, so wide levels
-    // take the overflow -> u16 re-run path)
-    const bool fits = ring_cap / 2u >= need1 || env_u32("OPENR_SPF_LEAN_FORCE", 0u, 0u, 1u) != 0u;
-    const bool lean = !has_ign && !a.tight && fits;
-    if (lean)
+    if (fp.lean) {
       err = launch_lvl_lean<MODE, BLOCK>(g, a, cost, ring_cap, blk, blk + 4, num_cus, s, info);
-    else
+      if (err == hipSuccess && a.dv.rows) err = launch_nh_derive(g, a, cost, blk + 4, num_cus, s);
+    } else {
       err = launch_lvl_variant<MODE, BLOCK, uint8_t, true, ELLM, SLICED>(g, a, cost, glog, has_ign, ring_cap, false,
                                                                          blk, blk + 4, num_cus, s, info);
+    }
   } else {
     err = launch_lvl_variant<MODE, BLOCK, uint8_t, true, ELLM, SLICED>(g, a, cost, glog, has_ign, ring_cap, false,
                                                                        blk, blk + 4, num_cus, s, info);
@@ -1366,6 +1417,18 @@ uint32_t bfs_lvl_lds_bytes(uint32_t V, uint32_t L, bool has_ignore, int cls) {
   const bool vis = cls == kLvlSliced || !nh_mode_single(mode);
   const uint32_t t = lvl_layout<uint16_t>(V, L, has_ignore, nh_words_for(mode, V), vis, V).total;
   return t <= kMaxLds ? t : 0;
+}
+
+// The choices of launch_bfs_lvl / launch_lvl_ell / launch_lvl_mode up to the pass, no launch.
+bool bfs_lvl_fast_pass(const DevGraph& g, const SolveArgs& a, int group_lanes, int num_cus) {
+  const bool has_ign = a.ign_ptr != nullptr;
+  const int cls = (int)a.cls;
+  if (cls == kLvlSliced || !bfs_lvl_lds_bytes(g.V, g.L, has_ign, cls) || a.n == 0) return false;
+  if (group_lanes > 1 || g.max_deg > 4u) return false;  // not ELL-only
+  const int mode = lvl_class_mode(cls);
+  const LvlShape sh = lvl_shape(g, has_ign, mode, false, kBfsTargetWgs);
+  const FastPass fp = lvl_fast_pass(g, a, mode, has_ign, sh.ring_cap, num_cus);
+  return fp.waves != 0u || fp.lean;
 }
 
 hipError_t launch_bfs_lvl(const DevGraph& g, const SolveArgs& a, uint64_t cost, int group_lanes, int num_cus,

@@ -84,6 +84,13 @@ struct Device {
   DevBuf<uint32_t> work;  // dynamic-scheduling counters (kWorkWords)
   DevBuf<uint32_t> status;  // sticky OPENR_SPF_STATUS_* bits of device-form calls
   DevBuf<uint32_t> perm, part;  // source-class partition of a batch
+  // split batches (spf_derive.hip): node -> sid, the classify flags and neighbour table, the solved / derived
+  // lists ([2n]), their class partition (+ the derived count at [2 * kMaxClasses]), the
+  // solved units' level rows and the epoch stamps that tell which call left them
+  DevBuf<uint32_t> dv_member, dv_nbrs, dv_perm, dv_part, dv_valid;
+  DevBuf<uint8_t> dv_flags, dv_rows;
+  uint32_t dv_epoch = 0;
+  bool dv_last = false;  // the last solve call on this device split its batch
   // what-if sweep: base SPF rows, the affected-unit work list, chunk result rows
   DevBuf<uint64_t> base_dist, base_tight, wdist;
   DevBuf<uint8_t> base_nh, wnh;
@@ -158,7 +165,8 @@ hipError_t reserve_counters(Device& d) {
 
 void free_graph(DevGraph& g) {
   void* ptrs[] = {g.row, g.row2, g.row2t, g.ovl_bits, g.ellt,    g.ellv,  g.adj,  g.w,    g.win, g.rev,
-                   g.lid, g.nbr,  g.ovl,   g.cls,      g.cls_lvl, g.ledge, g.rank, g.erec, g.w64, g.elld, g.erecs};
+                   g.lid, g.nbr,  g.ovl,   g.cls,      g.cls_lvl, g.ledge, g.rank, g.erec, g.w64, g.elld, g.erecs,
+                   g.derivable};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   g = DevGraph{};
@@ -352,11 +360,63 @@ int make_plan(const openr_spf_ctx* ctx, uint32_t flags, bool has_ign, Plan* p) {
 }
 
 
+// Split batches (spf_derive.hip): of a single-class lvl-family batch that asks for plain u64
+// distance and next-hop rows, only the sources that cover every link are solved; the rest
+// are derived from their neighbours' level rows. OPENR_SPF_DERIVE: 0 never, 1 wherever it
+// is legal, unset: batches above kDeriveAutoPerCu sources per CU. A batch of at most one
+// round of solves per CU cannot gain (its solved half takes the same one round): the wave
+// pass holds 8 solves per CU, and G100 on 256 CUs loses at 1 250 sources (0.150 -> 0.185 ms)
+// and gains from 2 500 on (0.255 -> 0.198 ms).
+// On success either a is unchanged (no split) or a.perm / a.part / a.dv describe the split.
+constexpr uint32_t kDeriveAutoPerCu = 8;
+constexpr uint64_t kDeriveRowsBudget = 1ull << 30;  // level-row scratch a device may hold
+hipError_t split_batch(Device& d, SolveArgs& a, int fam, int group_lanes, hipStream_t s) {
+  const char* env = std::getenv("OPENR_SPF_DERIVE");
+  const uint32_t knob = !env ? 2u : env[0] == '0' ? 0u : env[0] == '1' ? 1u : 2u;
+  if (knob == 0u || (knob == 2u && (uint64_t)a.n <= (uint64_t)kDeriveAutoPerCu * (uint64_t)std::max(d.num_cus, 1)))
+    return hipSuccess;
+  if (fam != kFamLvl || !a.dist || !a.nh || a.tight || a.ign_ptr || a.lvl_rows || a.lvl16 || a.target || a.seed_dist ||
+      a.out_row || a.order || a.n < 2u || prof_enabled())
+    return hipSuccess;
+  if (!bfs_lvl_fast_pass(d.g, a, group_lanes, d.num_cus)) return hipSuccess;
+  const uint32_t stride = (d.g.V + 15u) & ~15u;
+  if ((uint64_t)a.n * stride > kDeriveRowsBudget) return hipSuccess;
+  hipError_t err = d.dv_member.reserve(std::max<uint32_t>(d.g.V, 1u));
+  if (err == hipSuccess) err = d.dv_flags.reserve((size_t)a.n + 16u);
+  if (err == hipSuccess) err = d.dv_nbrs.reserve(2u * kDeriveMaxNbrs * (size_t)a.n);
+  if (err == hipSuccess) err = d.dv_perm.reserve(2u * (size_t)a.n);
+  if (err == hipSuccess) err = d.dv_part.reserve(2u * kMaxClasses + 1u);
+  if (err == hipSuccess) err = d.dv_rows.reserve((size_t)a.n * stride);
+  if (err == hipSuccess && (a.n > d.dv_valid.cap || d.dv_epoch == 0xFFFFFFFFu)) {
+    // stamps of no epoch: a fresh (or wrapped) buffer is zeroed, epochs start at 1
+    err = d.dv_valid.reserve(a.n);
+    if (err == hipSuccess) err = hipMemsetAsync(d.dv_valid.p, 0, d.dv_valid.cap * sizeof(uint32_t), s);
+    d.dv_epoch = 0;
+  }
+  if (err != hipSuccess) return err;
+  uint32_t* count = d.dv_part.p + 2u * kMaxClasses;
+  err = launch_derive_split(d.g, a.sources, a.n, a.cls, d.dv_member.p, d.dv_flags.p, d.dv_nbrs.p, d.dv_perm.p, d.dv_part.p, count,
+                            d.num_cus, s);
+  if (err != hipSuccess) return err;
+  a.perm = d.dv_perm.p;
+  a.part = d.dv_part.p;
+  a.dv.rows = d.dv_rows.p;
+  a.dv.stride = stride;
+  a.dv.epoch = ++d.dv_epoch;
+  a.dv.valid = d.dv_valid.p;
+  a.dv.nbrs = d.dv_nbrs.p;
+  a.dv.count = count;
+  d.dv_last = true;
+  return hipSuccess;
+}
+
 // Uniform-cost solves run per source class (next-hop width): one class -> one launch;
 // several -> a device-side partition of the batch, then one launch per class, the
 // widest first.
-hipError_t launch(const openr_spf_ctx* ctx, Device& d, const Plan& p, SolveArgs a, hipStream_t s) {
+hipError_t launch(const openr_spf_ctx* ctx, Device& d, const Plan& p, SolveArgs a, hipStream_t s,
+                  bool may_derive = false) {
   LaunchInfo info;
+  d.dv_last = false;
   if (p.exact) {  // writes every dist / nh / tight word itself
     const uint64_t slot = exact_slot_bytes(d.g.V, d.g.E, d.g.L, ctx->nh_bits);
     uint64_t bytes = 0;
@@ -417,6 +477,10 @@ hipError_t launch(const openr_spf_ctx* ctx, Device& d, const Plan& p, SolveArgs 
     if (a.dist_only && list) {  // part[cls] = listed count, part[kMaxClasses + cls] = 0
       a.perm = list;
       a.part = list_part;
+    }
+    if (may_derive && !list) {
+      hipError_t err = split_batch(d, a, fam, gl, s);
+      if (err != hipSuccess) return err;
     }
     return launch_bfs(fam, d.g, a, p.cost, gl, d.num_cus, s, &info);
   }
@@ -510,7 +574,7 @@ int solve_host(openr_spf_ctx* ctx, const uint32_t* sources, uint32_t n, uint32_t
     HIP_TRY(reserve_counters(d));
     a.work = d.work.p;
     HIP_TRY(hipEventRecord(d.ev_begin, d.stream));
-    HIP_TRY(launch(ctx, d, plan, a, d.stream));
+    HIP_TRY(launch(ctx, d, plan, a, d.stream, true));
     HIP_TRY(hipEventRecord(d.ev_end, d.stream));
     HIP_TRY(hipMemcpyAsync(dist + (size_t)b * V, d.dist.p, (size_t)m * V * sizeof(uint64_t),
                            hipMemcpyDeviceToHost, d.stream));
@@ -2934,6 +2998,13 @@ void openr_spf_destroy(openr_spf_ctx* ctx) {
     d.status.release();
     d.perm.release();
     d.part.release();
+    d.dv_member.release();
+    d.dv_nbrs.release();
+    d.dv_perm.release();
+    d.dv_part.release();
+    d.dv_valid.release();
+    d.dv_flags.release();
+    d.dv_rows.release();
     d.kkeep.release();
     d.ktloff.release();
     d.ktlent.release();
@@ -3111,6 +3182,20 @@ int openr_spf_set_graph(openr_spf_ctx* ctx, const openr_spf_graph* gr) {
     if (!cls_mask[f]) cls_mask[f] = 1u;  // no node: class 0
   const FrontierEstimate est = estimate_frontier(V, gr->row_ptr, adj.data(), ovl.data());
   if (w_min == UINT32_MAX) w_min = w_max = 1;  // no usable edge
+  // derive colouring (spf_derive.hip): greedy in node-id order, a node is derivable iff no
+  // structural neighbour (link up or down) already is and it has at most kDeriveMaxNbrs
+  // distinct neighbours. Independent in the link structure, so patches (attributes only)
+  // keep it valid; on a row-major grid it is the checkerboard.
+  std::vector<uint8_t> derivable(V, 0);
+  for (uint32_t u = 0; u < V; ++u) {
+    bool ok = true;
+    uint32_t nd = 0;
+    for (uint32_t e = gr->row_ptr[u]; e < gr->row_ptr[u + 1] && ok; ++e) {
+      nd = std::max<uint32_t>(nd, nbr[e] + 1u);
+      ok = gr->col[e] == u || !derivable[gr->col[e]];
+    }
+    derivable[u] = ok && nd <= kDeriveMaxNbrs;
+  }
 
   for (Device& d : ctx->devs) {
     HIP_TRY(hipSetDevice(d.ordinal));
@@ -3172,6 +3257,7 @@ int openr_spf_set_graph(openr_spf_ctx* ctx, const openr_spf_graph* gr) {
     if (err == hipSuccess) err = up(&g.lid, lid.data(), E);
     if (err == hipSuccess) err = up(&g.nbr, nbr.data(), E);
     if (err == hipSuccess) err = up(&g.ovl, ovl.data(), V);
+    if (err == hipSuccess) err = up(&g.derivable, derivable.data(), V);
     if (err == hipSuccess) err = up(&g.cls, cls[kFamCode].data(), V);
     if (err == hipSuccess) err = up(&g.cls_lvl, cls[kFamLvl].data(), V);
     if (err == hipSuccess) err = up(&g.ledge, ledge.data(), L);
@@ -3647,9 +3733,22 @@ int openr_spf_solve_device(openr_spf_ctx* ctx, int device_index, const uint32_t*
   HIP_TRY(reserve_counters(d));
   a.work = d.work.p;
   hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d.stream;
-  HIP_TRY(launch(ctx, d, plan, a, s));
+  HIP_TRY(launch(ctx, d, plan, a, s, true));
   ctx->stats.spf_runs += n;
   ctx->stats.batches += 1;
+  return OPENR_SPF_OK;
+}
+
+int openr_spf_last_derived(openr_spf_ctx* ctx, int device_index, uint32_t* out_derived) {
+  if (!ctx || !out_derived) return fail(OPENR_SPF_EINVAL, "null argument");
+  if (device_index < 0 || device_index >= (int)ctx->devs.size())
+    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+  Device& d = ctx->devs[device_index];
+  *out_derived = 0;
+  if (!d.dv_last) return OPENR_SPF_OK;
+  HIP_TRY(hipSetDevice(d.ordinal));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out_derived, d.dv_part.p + 2u * kMaxClasses, sizeof(uint32_t), hipMemcpyDeviceToHost));
   return OPENR_SPF_OK;
 }
 

@@ -45,6 +45,7 @@ struct DevGraph {
   uint32_t* lid = nullptr;     // [E] undirected link id
   uint16_t* nbr = nullptr;     // [E] distinct-neighbour index of col within its row
   uint8_t* ovl = nullptr;      // [V] overloaded
+  uint8_t* derivable = nullptr;  // [V] derive colouring: an independent set of the link structure (spf_derive.hip)
   uint8_t* cls = nullptr;      // [V] source class of each node, code family (SrcClass)
   uint8_t* cls_lvl = nullptr;  // [V] source class of each node, lvl family (LvlClass)
   uint2* ledge = nullptr;      // [L] the two directed edges of each link (UINT32_MAX if unused)
@@ -105,6 +106,23 @@ struct WhatifDelta {
   uint32_t cap = 0, nhb = 0;
   unsigned long long* used = nullptr;  // pool cursor (device counter, zeroed by the launcher)
   __device__ uint32_t base_of(unsigned long long b) const { return b < 0xFFFFFFFFull ? (uint32_t)b : 0xFFFFFFFFu; }
+};
+
+// Derived rows (spf_derive.hip): rows == null means the batch is not split. Solved units
+// leave their u8 level row at rows[sid * stride] and stamp valid[sid] = epoch; derived unit
+// j < *count is class-local index n + j of the launch's perm.
+// Distinct neighbours of a derivable node. Only the lean and the wave pass leave level rows,
+// and both need every row within the 4 ELL slots, so no split batch ever meets a wider node.
+constexpr uint32_t kDeriveMaxNbrs = 4;
+struct DeriveArgs {
+  uint8_t* rows;           // [n][stride] level rows of the solved units (0xFF: not reached)
+  uint32_t stride;         // bytes per row, a multiple of 16, >= V rounded up to 16
+  uint32_t epoch;          // this call's stamp (never 0)
+  uint32_t* valid;         // [n] epoch of the row each sid holds
+  // [n][2 * kDeriveMaxNbrs] per derived sid: its neighbour i when usable (else all ones), then the
+  // sid whose level row that neighbour contributes (all ones: none, it is overloaded)
+  const uint32_t* nbrs;
+  const uint32_t* count;   // device: derived units of the batch
 };
 
 struct SolveArgs {
@@ -186,6 +204,7 @@ struct SolveArgs {
   // sliced class with next-hop output, chunked: this launch solves the class-local solves
   // [k0, k0 + krows) and slice_tmp holds krows of them (row k - k0); krows 0 = the whole class
   uint32_t k0, krows;
+  DeriveArgs dv;  // lean / wave pass of a split batch (launch_derive_split), else zero
 };
 __host__ __device__ constexpr uint32_t ellv_rows(uint32_t V) { return V + 1u; }
 // output row of solve sid (SolveArgs::out_row)
@@ -231,6 +250,26 @@ hipError_t launch_bfs_code(const DevGraph& g, const SolveArgs& a, uint64_t cost,
                            hipStream_t s, LaunchInfo* info);
 hipError_t launch_bfs_lvl(const DevGraph& g, const SolveArgs& a, uint64_t cost, int group_lanes, int num_cus,
                           hipStream_t s, LaunchInfo* info);
+// true when launch_bfs_lvl runs the batch on the lean or the wave pass, the two passes that
+// can leave level rows for a split batch (SolveArgs::dv)
+bool bfs_lvl_fast_pass(const DevGraph& g, const SolveArgs& a, int group_lanes, int num_cus);
+
+// Derived rows (spf_derive.hip). For uniform cost the row of a source follows from the rows
+// of its neighbours, so of an all-sources batch only a set that covers every link needs a
+// BFS; the rule is in that file's header.
+// launch_derive_split: member[source] = sid, then entry i is derived iff its node is
+// derivable (DevGraph::derivable) and every neighbour it needs (link up, not overloaded) is
+// a source of the batch. perm[0 .. part[cls]) = the solved sids, perm[n .. n + *count) the
+// derived ones, both ascending; part[kMaxClasses + cls] = 0; nbrs as DeriveArgs::nbrs.
+// member: V u32 of scratch, flags: n + 16 bytes.
+hipError_t launch_derive_split(const DevGraph& g, const uint32_t* sources, uint32_t n, uint32_t cls, uint32_t* member,
+                               uint8_t* flags, uint32_t* nbrs, uint32_t* perm, uint32_t* part, uint32_t* count,
+                               int num_cus, hipStream_t s);
+// The derived rows of a.dv from the level rows the BFS launch left. A unit one of whose
+// neighbour rows is missing (its solve overflowed) is appended to a.ovf_list / *ovf_count
+// for the u16 re-run, as class-local index n + j.
+hipError_t launch_nh_derive(const DevGraph& g, const SolveArgs& a, uint64_t cost, uint32_t* ovf_count, int num_cus,
+                            hipStream_t s);
 
 // General positive metrics (spf_fringe.hip): one wavefront per solve, settle-safe
 // buckets of width delta = min usable metric over a fringe list, next hops pulled over

@@ -85,6 +85,7 @@ EXPORTS = (
     "openr_spf_refresh_device",
     "openr_spf_get_stats",
     "openr_spf_take_status",
+    "openr_spf_last_derived",
 )
 
 
@@ -329,6 +330,7 @@ def load_library():
     l.openr_spf_refresh_device.argtypes = [vp, ctypes.c_int, vp, u32, u32, vp, vp, u32, vp, vp, P(u32)]
     l.openr_spf_get_stats.argtypes = [vp, P(SpfStats)]
     l.openr_spf_take_status.argtypes = [vp, ctypes.c_int, P(u32)]
+    l.openr_spf_last_derived.argtypes = [vp, ctypes.c_int, P(u32)]
     for name in EXPORTS:
         if name not in ("openr_spf_last_error", "openr_spf_last_kernels", "openr_spf_limits", "openr_spf_destroy",
                         "openr_spf_build_id", "openr_spf_host_free"):
@@ -459,6 +461,13 @@ class SpfEngine:
         st = ctypes.c_uint32()
         _check(self._lib.openr_spf_take_status(self._ctx, device_index, ctypes.byref(st)))
         return int(st.value)
+
+    def last_derived(self, device_index: int = 0) -> int:
+        """Rows of the device's last solve call that were derived from their neighbours'
+        rows instead of solved (0: the batch was not split; waits for the device)."""
+        n = ctypes.c_uint32()
+        _check(self._lib.openr_spf_last_derived(self._ctx, device_index, ctypes.byref(n)))
+        return int(n.value)
 
     def whatif(self, links: Sequence[int], sources: Sequence[int], use_link_metric: bool = True
                ) -> Tuple[np.ndarray, int]:
