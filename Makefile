@@ -15,7 +15,7 @@ LIBDIR := openr_amd/lib
 CSRC := openr_amd/csrc
 
 ENGINE := $(LIBDIR)/libopenr_spf.so
-ENGINE_SRCS := $(CSRC)/spf_kernels.hip $(CSRC)/spf_bfs.hip $(CSRC)/spf_bfs_lvl.hip $(CSRC)/spf_derive.hip $(CSRC)/spf_sweep.hip $(CSRC)/spf_fringe.hip $(CSRC)/spf_rounds.hip $(CSRC)/spf_ksp.hip $(CSRC)/spf_update.hip $(CSRC)/spf_exact.hip $(CSRC)/spf_routes.hip $(CSRC)/spf_lfa.hip $(CSRC)/spf_wlfa.hip $(CSRC)/spf_drain.hip $(CSRC)/spf_metric.hip $(CSRC)/spf_restore.hip $(CSRC)/spf_elfa.hip $(CSRC)/spf_capi.hip
+ENGINE_SRCS := $(CSRC)/spf_kernels.hip $(CSRC)/spf_bfs.hip $(CSRC)/spf_bfs_lvl.hip $(CSRC)/spf_derive.hip $(CSRC)/spf_sweep.hip $(CSRC)/spf_fringe.hip $(CSRC)/spf_rounds.hip $(CSRC)/spf_ksp.hip $(CSRC)/spf_update.hip $(CSRC)/spf_exact.hip $(CSRC)/spf_routes.hip $(CSRC)/spf_lfa.hip $(CSRC)/spf_wlfa.hip $(CSRC)/spf_drain.hip $(CSRC)/spf_metric.hip $(CSRC)/spf_restore.hip $(CSRC)/spf_maint.hip $(CSRC)/spf_elfa.hip $(CSRC)/spf_capi.hip
 ENGINE_HDRS := $(CSRC)/spf_kernels.h $(CSRC)/spf_device.h $(CSRC)/spf_bfs_common.h $(CSRC)/spf_repair.h $(CSRC)/spf_restore_event.h include/openr_spf.h
 ENGINE_OBJS := $(patsubst $(CSRC)/%.hip,$(LIBDIR)/%.o,$(ENGINE_SRCS))
 

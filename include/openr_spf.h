@@ -689,8 +689,8 @@ int openr_spf_whatif_drain_lfa_device(openr_spf_ctx* ctx, int device_index, cons
    slice that is not strictly ascending, a metric below the current one or above 2^31 - 1,
    or n_events * n_sources > 2^32 - 1; OPENR_SPF_ENOTSUP when the base SPF needs the
    exact-order kernel (as openr_spf_whatif_drain); OPENR_SPF_E2BIG when a unit's state does
-   not fit LDS. Not covered: events that mix raises with overload bits or link-down sets.
-   Loop-free alternates under a metric event are openr_spf_whatif_metric_lfa below. Metric
+   not fit LDS. Events that mix raises with overload bits or link-down sets are
+   openr_spf_whatif_maint. Loop-free alternates under a metric event are openr_spf_whatif_metric_lfa below. Metric
    decreases are openr_spf_whatif_restore. */
 typedef struct {
   uint32_t n_events;
@@ -870,6 +870,99 @@ int openr_spf_whatif_restore_lfa_device(openr_spf_ctx* ctx, int device_index, co
                                         uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
                                         uint8_t* d_alt, uint64_t cap, uint32_t nh_bytes, void* stream,
                                         uint64_t* out_total, uint64_t* out_solved);
+
+/* Maintenance what-if sweep: what moves under a maintenance plan that mixes the worsening
+   kinds, e.g. router A hard-drained, its links to B out of service and neighbour C soft-drained
+   by +1000 in one window. A maintenance event i is three lists, each possibly empty: nodes N_i
+   that get the overload bit, links K_i taken out of service (Link::isUp() is false, both
+   directions), and directed CSR edges (the edge ids of openr_spf_patch_graph) with a new, higher
+   metric each. Unit (i, j) is runSpf(sources[j], useLinkMetric) on the graph patched with all
+   three, compared with the no-event SPF of sources[j]. With X = N_i minus the unit's source
+   minus the nodes that are overloaded already:
+     - removed edges: e = u -> v is removed iff link(e) is in K_i or u is in X;
+     - expansion: u may expand iff u is the source, or u is not overloaded and not in X;
+     - raised edges: R = the entries whose edge is up and whose new metric lies in
+       (w(e), 2^31 - 1]; w'(e) is the new metric if e is in R, else w(e);
+     - a base-tight edge is lost iff it is removed or raised. The repair (A, the seeds,
+       dist(A), D, the Kahn pass) is that of openr_spf_whatif_drain and openr_spf_whatif_metric,
+       with weights read through w' and usability through the removed set.
+   Each of these changes nothing:
+     - a raise on a removed edge, on a down edge, or on a row of an overloaded node other than
+       the unit's source;
+     - a new metric equal to the current one;
+     - a node that is overloaded already or is the unit's source (the source's row stays, and
+       raises on it act);
+     - an unused link id;
+     - a node, link or edge listed twice counts once; an empty event changes nothing;
+     - next-hop bit positions are those of the unmodified graph (openr_spf_neighbor_map).
+   Running the drain and the metric sweep apart and overlaying their deltas does not give this
+   answer. changed [n_events][n_sources] = nodes whose distance or next-hop bytes differ (a node
+   that becomes unreachable counts). No distance shrinks. delta (nullable: counts only) is the
+   CSR of openr_spf_whatif_sets_delta over units u = i * n_sources + j: node ids ascending;
+   OPENR_SPF_E2BIG means sum(changed) > cap and nothing else. *out_solved (nullable) = base
+   solves + affected units (units with a removed or really raised edge on a shortest path of
+   the source); it is added to stats.spf_runs. Events are split in contiguous blocks across the
+   context's devices.
+   Without OPENR_SPF_USE_LINK_METRIC every weight is 1 and the metric entries are ignored; the
+   kernels still run for N_i and K_i.
+   Errors: OPENR_SPF_EINVAL for a null or non-ascending node_ptr / link_ptr / edge_ptr (the
+   last two may be NULL), a node >= V, a link >= L, an edge >= E, an event's edge slice that
+   is not strictly ascending, a new metric below the current one (a decrease is a restore
+   event) or above 2^31 - 1, or n_events * n_sources > 2^32 - 1; OPENR_SPF_ENOTSUP when the
+   base SPF needs the exact-order kernel (as openr_spf_whatif_drain; the hop-count form of such
+   a graph is served); OPENR_SPF_E2BIG when a unit's state does not fit LDS. Not covered: events
+   that mix worsening with restoring changes, exact-order base plans, the C++ LinkState mirror,
+   and a loop-free-alternate form of this sweep (openr_spf_whatif_drain_lfa and its siblings
+   take one family's events each). */
+typedef struct {
+  uint32_t n_events;
+  const uint32_t* node_ptr;  /* [n_events + 1] */
+  const uint32_t* nodes;     /* nodes that get the overload bit */
+  const uint32_t* link_ptr;  /* nullable: no links in any event; else [n_events + 1] */
+  const uint32_t* links;     /* links taken out of service */
+  const uint32_t* edge_ptr;  /* nullable: no metric entries in any event; else [n_events + 1] */
+  const uint32_t* edges;     /* directed CSR edge ids, strictly ascending inside an event */
+  const uint32_t* metrics;   /* the new metric of edges[k], >= the current one */
+} openr_spf_maint_events_t;
+int openr_spf_whatif_maint(openr_spf_ctx* ctx, const openr_spf_maint_events_t* events, const uint32_t* sources,
+                           uint32_t n_sources, uint32_t flags, uint32_t* changed, openr_spf_whatif_delta_t* delta,
+                           uint64_t* out_solved);
+
+/* Device-buffer form (every buffer device memory), conventions of openr_spf_whatif_restore_device:
+   d_nodes holds n_nodes entries, d_links n_links (d_link_ptr NULL: no links), d_edges and
+   d_metrics n_edges (d_edge_ptr NULL: no metric entries). Nothing is validated: every slice is
+   clamped to its array; an id out of range, an unused link and an entry whose metric is not in
+   (current, 2^31 - 1] are skipped. For an edge slice that does not ascend, which of its entries
+   take effect is unspecified; nothing is read out of bounds and every loop terminates. Cap,
+   OPENR_SPF_E2BIG, *out_total and the order of a unit's entries are those of
+   openr_spf_whatif_drain_device. Synchronizes `stream`. */
+int openr_spf_whatif_maint_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
+                                  const uint32_t* d_nodes, const uint32_t* d_link_ptr, const uint32_t* d_links,
+                                  const uint32_t* d_edge_ptr, const uint32_t* d_edges, const uint32_t* d_metrics,
+                                  uint32_t n_events, uint32_t n_nodes, uint32_t n_links, uint32_t n_edges,
+                                  const uint32_t* d_sources, uint32_t n_sources, uint32_t flags, uint32_t* d_changed,
+                                  uint64_t* d_ptr, uint32_t* d_node, uint64_t* d_dist, uint8_t* d_nh, uint64_t cap,
+                                  uint32_t nh_bytes, void* stream, uint64_t* out_total, uint64_t* out_solved);
+
+/* The same sweep resolved to routes over a group table: outputs, route rule and errors of
+   openr_spf_whatif_routes[_device], units and errors of openr_spf_whatif_maint[_device]. A
+   route can turn unreachable under a maintenance event (through K_i); a drained node's own
+   prefixes stay reachable wherever the node is. */
+int openr_spf_whatif_maint_routes(openr_spf_ctx* ctx, const openr_spf_maint_events_t* events,
+                                  const uint32_t* sources, uint32_t n_sources, uint32_t flags,
+                                  const openr_spf_groups_t* groups, uint32_t* changed_routes,
+                                  openr_spf_whatif_routes_t* delta, uint64_t* out_solved);
+int openr_spf_whatif_maint_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
+                                         const uint32_t* d_nodes, const uint32_t* d_link_ptr,
+                                         const uint32_t* d_links, const uint32_t* d_edge_ptr,
+                                         const uint32_t* d_edges, const uint32_t* d_metrics, uint32_t n_events,
+                                         uint32_t n_nodes, uint32_t n_links, uint32_t n_edges,
+                                         const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                                         const uint32_t* d_group_ptr, const uint32_t* d_group_nodes,
+                                         uint32_t n_groups, uint32_t n_group_nodes, uint32_t* d_changed_routes,
+                                         uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
+                                         uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes, void* stream,
+                                         uint64_t* out_total, uint64_t* out_solved);
 
 /* LinkState::getKthPaths(src[i], dst[i], 1) and (.., 2) (LinkState.cpp:762-791, with
    traceOnePath :398-419) for a batch of pairs, traced on the device. Per pair, tok1 /

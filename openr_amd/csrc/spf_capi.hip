@@ -1197,6 +1197,9 @@ struct WhatifUnits {
   // restore events: the three CSRs above together (node_ptr set; set_ptr / edge_ptr nullable),
   // the nodes undrained, the links put back, the metrics lowered
   bool restore = false;
+  // maintenance events: the three CSRs together as well, the nodes overloaded, the links taken
+  // out of service, the metrics raised
+  bool maint = false;
 };
 
 // Event sweep on one device (openr_spf_whatif_drain / _metric / _restore; spf_drain.hip,
@@ -1305,6 +1308,25 @@ hipError_t whatif_restore_on_device(openr_spf_ctx* ctx, Device& d, const Plan& b
                                  launch_restore_repair, d_sources, n_src, d_changed, s, solved, dl);
 }
 
+hipError_t whatif_maint_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, const WhatifUnits& un,
+                                  const uint32_t* d_sources, uint32_t n_src, uint32_t* d_changed, hipStream_t s,
+                                  uint32_t* solved, bool use_link_metric, const WhatifDelta& dl) {
+  MaintPass p{};
+  p.n_nodes = un.n_nodes;
+  p.n_links = un.n_set_links;
+  p.n_edges = un.n_edges;
+  p.unit_cost = use_link_metric ? 0u : 1u;
+  p.node_ptr = un.node_ptr;
+  p.nodes = un.nodes;
+  p.link_ptr = un.set_ptr;
+  p.links = un.set_links;
+  p.edge_ptr = un.edge_ptr;
+  p.edges = un.edges;
+  p.metrics = un.metrics;
+  return whatif_repair_on_device(ctx, d, base_plan, p, un.n, kMaintCtr, launch_maint_filter, launch_maint_repair,
+                                 d_sources, n_src, d_changed, s, solved, dl);
+}
+
 // Plan and capacity checks of the drain and metric calls (`word`): the repair reads base_tight
 // rows, which the exact-order kernel's history-dependent pop order does not give a meaning the
 // rule can use. lds(V, dim, S, nb) is the kind's LDS size, dim its L or E (`dim_name`).
@@ -1340,11 +1362,21 @@ int check_restore(const openr_spf_ctx* ctx, uint32_t flags, uint64_t n_events, u
       restore_slots(), 'E', ctx->E);
 }
 
+int check_maint(const openr_spf_ctx* ctx, uint32_t flags, uint64_t n_events, uint64_t n_sources) {
+  const uint32_t L = ctx->L;
+  return check_repair_sweep(
+      ctx, flags, n_events, n_sources, "maintenance",
+      [L](uint32_t V, uint32_t E, uint32_t S, uint32_t nb) { return maint_lds_bytes(V, L, E, S, nb); },
+      maint_slots(), 'E', ctx->E);
+}
+
 hipError_t whatif_units_on_device(openr_spf_ctx* ctx, Device& d, const Plan& bp, const Plan& ip, const WhatifUnits& un,
                                   const uint32_t* d_sources, uint32_t n_src, uint32_t* d_changed, hipStream_t s,
                                   uint32_t* solved, bool use_link_metric, const WhatifDelta& dl = WhatifDelta{}) {
   if (un.restore)
     return whatif_restore_on_device(ctx, d, bp, un, d_sources, n_src, d_changed, s, solved, use_link_metric, dl);
+  if (un.maint)
+    return whatif_maint_on_device(ctx, d, bp, un, d_sources, n_src, d_changed, s, solved, use_link_metric, dl);
   if (un.edge_ptr)
     return whatif_metric_on_device(ctx, d, bp, un, d_sources, n_src, d_changed, s, solved, use_link_metric, dl);
   if (un.node_ptr)
@@ -1395,7 +1427,8 @@ int whatif_delta_on_device(openr_spf_ctx* ctx, Device& d, const WhatifUnits& un,
   dl.cap = (uint32_t)want;
   dl.nhb = nhb;
   dl.used = d.dl_used.p;
-  if ((un.node_ptr || un.edge_ptr) && !cap) dl.node = nullptr;  // drain / metric sweep, counts and ptr only: the repair writes no entries
+  // drain / metric / restore / maintenance sweep, counts and ptr only: the repair writes no entries
+  if ((un.node_ptr || un.edge_ptr || un.maint) && !cap) dl.node = nullptr;
   uint32_t solved = 0;
   HIP_TRY(whatif_units_on_device(ctx, d, bp, ip, un, d_sources, n_src, d_changed, s, &solved,
                                  (flags & OPENR_SPF_USE_LINK_METRIC) != 0, dl));
@@ -1428,7 +1461,8 @@ int check_whatif_host(const openr_spf_ctx* ctx, const WhatifUnits& hu, const uin
     return fail(OPENR_SPF_EINVAL, "null links, sources or changed");
   for (uint32_t i = 0; i < n_sources; ++i)
     if (sources[i] >= ctx->V) return fail(OPENR_SPF_EINVAL, "source %u out of range (V=%u)", sources[i], ctx->V);
-  if (hu.restore) {  // restore events: node CSR, link CSR (nullable), edge CSR (nullable) with lowers only
+  // restore / maintenance events: node CSR, link CSR (nullable), edge CSR (nullable) with lowers / raises only
+  if (hu.restore || hu.maint) {
     if (hu.n && !hu.node_ptr) return fail(OPENR_SPF_EINVAL, "null node_ptr");
     for (uint32_t i = 0; i < hu.n; ++i) {
       if (hu.node_ptr[i + 1] < hu.node_ptr[i]) return fail(OPENR_SPF_EINVAL, "node_ptr does not ascend at event %u", i);
@@ -1455,6 +1489,14 @@ int check_whatif_host(const openr_spf_ctx* ctx, const WhatifUnits& hu, const uin
           if (e >= ctx->E) return fail(OPENR_SPF_EINVAL, "edge %u out of range (E=%u)", e, ctx->E);
           if (k > hu.edge_ptr[i] && e <= hu.edges[k - 1])
             return fail(OPENR_SPF_EINVAL, "event %u: edge ids are not strictly ascending", i);
+          if (hu.maint) {
+            if (hu.metrics[k] < ctx->metric[e] || hu.metrics[k] > 0x7FFFFFFFu)
+              return fail(OPENR_SPF_EINVAL,
+                          "event %u: metric %u of edge %u is below the current one (%llu: a decrease belongs to "
+                          "openr_spf_whatif_restore) or above 2^31-1",
+                          i, hu.metrics[k], e, (unsigned long long)ctx->metric[e]);
+            continue;
+          }
           if (hu.metrics[k] > ctx->metric[e] || hu.metrics[k] < 1u)
             return fail(OPENR_SPF_EINVAL,
                         "event %u: metric %u of edge %u is above the current one (%llu: a raise belongs to "
@@ -1508,7 +1550,8 @@ int upload_whatif_units(Device& d, const WhatifUnits& hu, uint32_t b, uint32_t m
                         WhatifUnits* un) {
   *un = WhatifUnits{};
   un->n = m;
-  if (hu.restore) {  // restore events: win_ptr / win_nodes, win_lptr / win_links, win_eptr / win_edges / win_metrics
+  // restore / maintenance events: win_ptr / win_nodes, win_lptr / win_links, win_eptr / win_edges / win_metrics
+  if (hu.restore || hu.maint) {
     // one CSR's block: ptr rebased to the block's slice, the slice of vals (and vals2) behind it
     auto block = [&](const uint32_t* ptr, const uint32_t* vals, const uint32_t* vals2, DevBuf<uint32_t>& dptr,
                      DevBuf<uint32_t>& dvals, DevBuf<uint32_t>* dvals2, uint32_t* count) -> int {
@@ -1528,7 +1571,8 @@ int upload_whatif_units(Device& d, const WhatifUnits& hu, uint32_t b, uint32_t m
       *count = e0 - b0;
       return OPENR_SPF_OK;
     };
-    un->restore = true;
+    un->restore = hu.restore;
+    un->maint = hu.maint;
     int rc = block(hu.node_ptr, hu.nodes, nullptr, d.win_ptr, d.win_nodes, nullptr, &un->n_nodes);
     if (rc) return rc;
     un->node_ptr = d.win_ptr.p;
@@ -1884,6 +1928,18 @@ WhatifUnits restore_units(const uint32_t* node_ptr, const uint32_t* nodes, const
   un.metrics = metrics;
   un.n_edges = n_edges;
   un.restore = true;
+  return un;
+}
+
+// Maintenance events as what-if units: the CSRs of restore_units, read as overloads, link-downs and raises.
+WhatifUnits maint_units(const uint32_t* node_ptr, const uint32_t* nodes, const uint32_t* link_ptr,
+                        const uint32_t* links, const uint32_t* edge_ptr, const uint32_t* edges,
+                        const uint32_t* metrics, uint32_t n_events, uint32_t n_nodes, uint32_t n_links,
+                        uint32_t n_edges) {
+  WhatifUnits un = restore_units(node_ptr, nodes, link_ptr, links, edge_ptr, edges, metrics, n_events, n_nodes,
+                                 n_links, n_edges);
+  un.restore = false;
+  un.maint = true;
   return un;
 }
 
@@ -4166,6 +4222,107 @@ int openr_spf_whatif_restore_routes_device(openr_spf_ctx* ctx, int device_index,
   rc = whatif_routes_on_device(ctx, d,
                                restore_units(d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics,
                                              n_events, n_nodes, n_links, n_edges),
+                               d_sources, n_sources, flags, gr, d_changed_routes, d_ptr, d_group, d_metric, d_nh,
+                               d_n_best, cap, nh_bytes, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream,
+                               &total, &solved);
+  if (out_total) *out_total = total;
+  if (out_solved) *out_solved = solved;
+  return rc;
+}
+
+// Host-form checks of a maintenance call, in the order EINVAL, then the plan's ENOTSUP / E2BIG.
+static int check_maint_host(openr_spf_ctx* ctx, const openr_spf_maint_events_t* ev, const uint32_t* sources,
+                            uint32_t n_sources, uint32_t flags, const uint32_t* changed, WhatifUnits* hu) {
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (!ev) return fail(OPENR_SPF_EINVAL, "null events");
+  if (ev->n_events && !ev->node_ptr) return fail(OPENR_SPF_EINVAL, "null node_ptr");
+  *hu = maint_units(ev->node_ptr, ev->nodes, ev->link_ptr, ev->links, ev->edge_ptr, ev->edges, ev->metrics,
+                    ev->n_events, 0u, 0u, 0u);
+  const int rc = check_whatif_host(ctx, *hu, sources, n_sources, changed);
+  return rc ? rc : check_maint(ctx, flags, ev->n_events, n_sources);
+}
+
+int openr_spf_whatif_maint(openr_spf_ctx* ctx, const openr_spf_maint_events_t* events, const uint32_t* sources,
+                           uint32_t n_sources, uint32_t flags, uint32_t* changed, openr_spf_whatif_delta_t* delta,
+                           uint64_t* out_solved) {
+  clear_launch_trace();
+  WhatifUnits hu;
+  int rc = check_maint_host(ctx, events, sources, n_sources, flags, changed, &hu);
+  if (rc) return rc;
+  if (!delta) return whatif_host(ctx, hu, sources, n_sources, flags, changed, out_solved);
+  return whatif_delta_host(ctx, hu, sources, n_sources, flags, changed, delta, out_solved);
+}
+
+int openr_spf_whatif_maint_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
+                                  const uint32_t* d_nodes, const uint32_t* d_link_ptr, const uint32_t* d_links,
+                                  const uint32_t* d_edge_ptr, const uint32_t* d_edges, const uint32_t* d_metrics,
+                                  uint32_t n_events, uint32_t n_nodes, uint32_t n_links, uint32_t n_edges,
+                                  const uint32_t* d_sources, uint32_t n_sources, uint32_t flags, uint32_t* d_changed,
+                                  uint64_t* d_ptr, uint32_t* d_node, uint64_t* d_dist, uint8_t* d_nh, uint64_t cap,
+                                  uint32_t nh_bytes, void* stream, uint64_t* out_total, uint64_t* out_solved) {
+  clear_launch_trace();
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (n_events && (!d_node_ptr || (n_nodes && !d_nodes) || (d_link_ptr && n_links && !d_links) ||
+                   (d_edge_ptr && n_edges && (!d_edges || !d_metrics))))
+    return fail(OPENR_SPF_EINVAL, "null node_ptr, nodes, links, edges or metrics");
+  int rc = check_maint(ctx, flags, n_events, n_sources);
+  if (rc) return rc;
+  return whatif_delta_device_form(ctx, device_index,
+                                  maint_units(d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges,
+                                              d_metrics, n_events, n_nodes, n_links, n_edges),
+                                  d_sources, n_sources, flags, d_changed, d_ptr, d_node, d_dist, d_nh, cap, nh_bytes,
+                                  stream, out_total, out_solved);
+}
+
+int openr_spf_whatif_maint_routes(openr_spf_ctx* ctx, const openr_spf_maint_events_t* events,
+                                  const uint32_t* sources, uint32_t n_sources, uint32_t flags,
+                                  const openr_spf_groups_t* groups, uint32_t* changed_routes,
+                                  openr_spf_whatif_routes_t* delta, uint64_t* out_solved) {
+  clear_launch_trace();
+  WhatifUnits hu;
+  int rc = check_maint_host(ctx, events, sources, n_sources, flags, changed_routes, &hu);
+  if (rc) return rc;
+  return whatif_routes_host(ctx, hu, sources, n_sources, flags, groups, changed_routes, delta, out_solved);
+}
+
+int openr_spf_whatif_maint_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
+                                         const uint32_t* d_nodes, const uint32_t* d_link_ptr,
+                                         const uint32_t* d_links, const uint32_t* d_edge_ptr,
+                                         const uint32_t* d_edges, const uint32_t* d_metrics, uint32_t n_events,
+                                         uint32_t n_nodes, uint32_t n_links, uint32_t n_edges,
+                                         const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                                         const uint32_t* d_group_ptr, const uint32_t* d_group_nodes,
+                                         uint32_t n_groups, uint32_t n_group_nodes, uint32_t* d_changed_routes,
+                                         uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
+                                         uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes, void* stream,
+                                         uint64_t* out_total, uint64_t* out_solved) {
+  clear_launch_trace();
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (device_index < 0 || device_index >= (int)ctx->devs.size())
+    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+  if ((n_events && (!d_node_ptr || (n_nodes && !d_nodes) || (d_link_ptr && n_links && !d_links) ||
+                    (d_edge_ptr && n_edges && (!d_edges || !d_metrics)))) ||
+      (n_sources && !d_sources) || (n_events && n_sources && !d_changed_routes) || !d_ptr)
+    return fail(OPENR_SPF_EINVAL, "null events, sources, changed_routes or ptr");
+  if ((n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes))
+    return fail(OPENR_SPF_EINVAL, "null group_ptr or group_nodes");
+  if (cap && (!d_group || !d_metric || !d_nh)) return fail(OPENR_SPF_EINVAL, "null route buffer");
+  int rc = check_maint(ctx, flags, n_events, n_sources);
+  if (rc) return rc;
+  Device& d = ctx->devs[device_index];
+  HIP_TRY(hipSetDevice(d.ordinal));
+  DevGroups gr;
+  gr.ptr = d_group_ptr;
+  gr.nodes = d_group_nodes;
+  gr.n = n_groups;
+  gr.m = n_group_nodes;
+  uint64_t total = 0, solved = 0;
+  rc = whatif_routes_on_device(ctx, d,
+                               maint_units(d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics,
+                                           n_events, n_nodes, n_links, n_edges),
                                d_sources, n_sources, flags, gr, d_changed_routes, d_ptr, d_group, d_metric, d_nh,
                                d_n_best, cap, nh_bytes, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream,
                                &total, &solved);

@@ -564,7 +564,8 @@ struct MetricPass : RepairPass {
 };
 constexpr uint32_t kMetricCtr = kDrainCtr + 2;
 constexpr uint32_t kRestoreCtr = kMetricCtr + 2;
-constexpr uint32_t kWorkWords = kRestoreCtr + 2;  // the counter buffer: the class blocks, then one pair per sweep kernel
+constexpr uint32_t kMaintCtr = kRestoreCtr + 2;
+constexpr uint32_t kWorkWords = kMaintCtr + 2;  // the counter buffer: the class blocks, then one pair per sweep kernel
 static_assert(kDrainCtr + 2 == kWorkSlots, "the metric sweep's counters follow the last class block");
 constexpr uint32_t kMetricSlots = 256;      // dirty-node slots of the narrow launch (OPENR_SPF_METRIC_SLOTS)
 constexpr uint32_t kMetricBlock = 64;       // threads per unit, narrow launch
@@ -605,6 +606,33 @@ uint32_t restore_lds_bytes(uint32_t V, uint32_t L, uint32_t E, uint32_t S, uint3
 hipError_t launch_restore_filter(const DevGraph& g, const RestorePass& p, int num_cus, hipStream_t s);
 hipError_t launch_restore_repair(const DevGraph& g, const RestorePass& p, uint32_t count, bool rerun, int num_cus,
                                  hipStream_t s);
+
+// Maintenance what-if sweep (spf_maint.hip): unit u = i * n_src + j overloads event i's nodes,
+// takes its links out of service and raises the metrics of its directed edges (three CSRs as
+// the drain's and the metric pass's; null link_ptr / edge_ptr: none) for sources[j]; the rule
+// is in that file's header and at openr_spf_whatif_maint. Slices are clamped to n_nodes /
+// n_links / n_edges entries; an id out of range, an unused link, an entry whose edge is down
+// or whose metric is not in (current, 2^31 - 1] are skipped. unit_cost: the entries are ignored.
+struct MaintPass : RepairPass {
+  uint32_t n_nodes, n_links, n_edges, unit_cost;
+  const uint32_t* node_ptr;
+  const uint32_t* nodes;
+  const uint32_t* link_ptr;
+  const uint32_t* links;
+  const uint32_t* edge_ptr;
+  const uint32_t* edges;
+  const uint32_t* metrics;
+};
+constexpr uint32_t kMaintSlots = 256;      // dirty-node slots of the narrow launch (OPENR_SPF_MAINT_SLOTS)
+constexpr uint32_t kMaintBlock = 64;       // threads per unit, narrow launch
+constexpr uint32_t kMaintBlockWide = 256;  // ... and the re-run with a slot per node
+uint32_t maint_slots();
+// As drain_lds_bytes, with V bits for the drained nodes, L for the links and E for the raised edges.
+uint32_t maint_lds_bytes(uint32_t V, uint32_t L, uint32_t E, uint32_t S, uint32_t nb);
+// The launchers as the drain's; the filter lists the units with a removed or raised base-tight edge.
+hipError_t launch_maint_filter(const DevGraph& g, const MaintPass& p, int num_cus, hipStream_t s);
+hipError_t launch_maint_repair(const DevGraph& g, const MaintPass& p, uint32_t count, bool rerun, int num_cus,
+                               hipStream_t s);
 
 // Loop-free alternates under drain, metric and restore events (spf_elfa.hip): the pass of
 // spf_wlfa.hip over the node deltas of an event sweep (events x closure rows). The rule is in

@@ -76,6 +76,10 @@ EXPORTS = (
     "openr_spf_whatif_restore_routes_device",
     "openr_spf_whatif_restore_lfa",
     "openr_spf_whatif_restore_lfa_device",
+    "openr_spf_whatif_maint",
+    "openr_spf_whatif_maint_device",
+    "openr_spf_whatif_maint_routes",
+    "openr_spf_whatif_maint_routes_device",
     "openr_spf_ksp2",
     "openr_spf_ksp2_device",
     "openr_spf_host_alloc",
@@ -208,6 +212,10 @@ class RestoreEvents(ctypes.Structure):  # openr_spf_restore_events_t
     ]
 
 
+class MaintEvents(ctypes.Structure):  # openr_spf_maint_events_t
+    _fields_ = list(RestoreEvents._fields_)
+
+
 class SpfLimits(ctypes.Structure):
     _fields_ = [("max_nodes", ctypes.c_uint32), ("max_nh_bits", ctypes.c_uint32)]
 
@@ -309,6 +317,10 @@ def load_library():
                                                          u32, vp, u32, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp,
                                                          ctypes.c_uint64, u32, vp, P(ctypes.c_uint64),
                                                          P(ctypes.c_uint64)]
+    l.openr_spf_whatif_maint.argtypes = [vp, P(MaintEvents)] + l.openr_spf_whatif_restore.argtypes[2:]
+    l.openr_spf_whatif_maint_device.argtypes = l.openr_spf_whatif_restore_device.argtypes
+    l.openr_spf_whatif_maint_routes.argtypes = [vp, P(MaintEvents)] + l.openr_spf_whatif_restore_routes.argtypes[2:]
+    l.openr_spf_whatif_maint_routes_device.argtypes = l.openr_spf_whatif_restore_routes_device.argtypes
     # event arguments as the family's _routes[_device] call, then those of whatif_lfa[_device]
     lfa_host = [vp, u32, u32, P(SpfGroups), vp, vp, vp, P(WhatifLfa), P(ctypes.c_uint64)]
     lfa_dev = [vp, u32, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_uint64, u32, vp,
@@ -1043,10 +1055,11 @@ class SpfEngine:
         return int(total.value), int(solved.value)
 
     @staticmethod
-    def _restore_events(node_sets, link_sets, edge_sets, metric_sets):
+    def _restore_events(node_sets, link_sets, edge_sets, metric_sets, struct=RestoreEvents):
         """(RestoreEvents, the arrays it points into) of per-event node, link, edge and
         new-metric lists (as given: topology.restore_events sorts and merges them). None for
-        a kind: no entry of it in any event."""
+        a kind: no entry of it in any event. struct=MaintEvents: the same lists as a
+        maintenance event (topology.maint_events)."""
         if (edge_sets is None) != (metric_sets is None):
             raise ValueError("edge_sets and metric_sets go together")
         counts = {len(x) for x in (node_sets, link_sets, edge_sets, metric_sets) if x is not None}
@@ -1060,7 +1073,7 @@ class SpfEngine:
         ep, ee = _ignore_arrays(edge_sets, n) if edge_sets is not None else (None, None)
         mm = _ignore_arrays(metric_sets, n)[1] if metric_sets is not None else None
         keep = (np_, nn, lp, ll, ep, ee, mm)
-        return RestoreEvents(n, *(_p(a) for a in keep)), keep, n
+        return struct(n, *(_p(a) for a in keep)), keep, n
 
     def whatif_restore(self, node_sets: Optional[Sequence[Sequence[int]]], link_sets: Optional[Sequence[Sequence[int]]],
                        edge_sets: Optional[Sequence[Sequence[int]]], metric_sets: Optional[Sequence[Sequence[int]]],
@@ -1164,6 +1177,119 @@ class SpfEngine:
         solved = ctypes.c_uint64()
         flags = USE_LINK_METRIC if use_link_metric else 0
         rc = self._lib.openr_spf_whatif_restore_routes_device(
+            self._ctx, device_index, vp(d_node_ptr or None), vp(d_nodes or None), vp(d_link_ptr or None),
+            vp(d_links or None), vp(d_edge_ptr or None), vp(d_edges or None), vp(d_metrics or None), n_events, n_nodes,
+            n_links, n_edges, vp(d_sources), n_sources, flags, vp(d_group_ptr or None), vp(d_group_nodes or None),
+            n_groups, n_group_nodes, vp(d_changed), vp(d_ptr), vp(d_group or None), vp(d_metric or None),
+            vp(d_nh or None), vp(d_n_best or None), cap, nh_bytes, vp(stream or None), ctypes.byref(total),
+            ctypes.byref(solved))
+        if not (allow_overflow and rc == E2BIG):
+            _check(rc)
+        return int(total.value), int(solved.value)
+
+    # ---- maintenance events: overloads, link-downs and metric raises together ---------------
+    def whatif_maint(self, node_sets: Optional[Sequence[Sequence[int]]], link_sets: Optional[Sequence[Sequence[int]]],
+                     edge_sets: Optional[Sequence[Sequence[int]]], metric_sets: Optional[Sequence[Sequence[int]]],
+                     sources: Sequence[int], use_link_metric: bool = True, want_delta: bool = True,
+                     cap: Optional[int] = None, nh_bytes: Optional[int] = None):
+        """Maintenance sweep (openr_spf_whatif_maint): event i overloads the nodes of
+        node_sets[i], takes the links of link_sets[i] out of service and gives the directed
+        edge edge_sets[i][k] the higher metric metric_sets[i][k] (see topology.maint_events);
+        None for a kind: none of it. Unit u = i * n_sources + j. Returns the shape of
+        whatif_metric: (changed[n_events, n_sources] u32, ptr, node, dist, nh, solved), or
+        (changed, solved) with want_delta=False. cap None: sized from a count-only pass."""
+        ev, keep, n = self._restore_events(node_sets, link_sets, edge_sets, metric_sets, MaintEvents)
+        src = np.ascontiguousarray(sources, dtype=np.uint32)
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
+        solved = ctypes.c_uint64()
+        if not want_delta or cap is None:
+            _check(self._lib.openr_spf_whatif_maint(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
+                                                    _p(changed), None, ctypes.byref(solved)))
+            if not want_delta:
+                return changed, int(solved.value)
+            cap = int(changed.sum(dtype=np.uint64))
+        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
+        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
+        node = np.zeros(max(cap, 1), dtype=np.uint32)
+        dist = np.zeros(max(cap, 1), dtype=np.uint64)
+        nh = np.zeros((max(cap, 1), nb), dtype=np.uint8)
+        d = WhatifDelta(_p(ptr), _p(node), _p(dist), _p(nh), cap, nb)
+        _check(self._lib.openr_spf_whatif_maint(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
+                                                _p(changed), ctypes.byref(d), ctypes.byref(solved)))
+        del keep
+        k = int(ptr[-1])
+        return changed, ptr, node[:k], dist[:k], nh[:k], int(solved.value)
+
+    def whatif_maint_device(self, d_node_ptr: int, d_nodes: int, d_link_ptr: int, d_links: int, d_edge_ptr: int,
+                            d_edges: int, d_metrics: int, n_events: int, n_nodes: int, n_links: int, n_edges: int,
+                            d_sources: int, n_sources: int, d_changed: int, d_ptr: int, d_node: int, d_dist: int,
+                            d_nh: int, cap: int, nh_bytes: int, use_link_metric: bool = True, stream: int = 0,
+                            device_index: int = 0, allow_overflow: bool = False) -> Tuple[int, int]:
+        """Device-pointer form: (total entries, solved). d_link_ptr / d_edge_ptr 0: no links /
+        no metric entries. d_ptr [n_units + 1] u64 CSR; unit u's entries are [ptr[u],
+        ptr[u + 1]) in the kernel's order."""
+        vp = ctypes.c_void_p
+        total = ctypes.c_uint64()
+        solved = ctypes.c_uint64()
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        rc = self._lib.openr_spf_whatif_maint_device(
+            self._ctx, device_index, vp(d_node_ptr or None), vp(d_nodes or None), vp(d_link_ptr or None),
+            vp(d_links or None), vp(d_edge_ptr or None), vp(d_edges or None), vp(d_metrics or None), n_events, n_nodes,
+            n_links, n_edges, vp(d_sources), n_sources, flags, vp(d_changed), vp(d_ptr), vp(d_node or None),
+            vp(d_dist or None), vp(d_nh or None), cap, nh_bytes, vp(stream or None), ctypes.byref(total),
+            ctypes.byref(solved))
+        if not (allow_overflow and rc == E2BIG):
+            _check(rc)
+        return int(total.value), int(solved.value)
+
+    def whatif_maint_routes(self, node_sets: Optional[Sequence[Sequence[int]]],
+                            link_sets: Optional[Sequence[Sequence[int]]],
+                            edge_sets: Optional[Sequence[Sequence[int]]],
+                            metric_sets: Optional[Sequence[Sequence[int]]], sources: Sequence[int],
+                            groups: Sequence[Sequence[int]], use_link_metric: bool = True,
+                            cap: Optional[int] = None, nh_bytes: Optional[int] = None):
+        """The maintenance sweep resolved to routes (openr_spf_whatif_maint_routes): the return
+        shape of whatif_routes. cap None: sized from a count-only pass."""
+        ev, keep, n = self._restore_events(node_sets, link_sets, edge_sets, metric_sets, MaintEvents)
+        gp, gn = _ignore_arrays(groups, len(groups))
+        gs = SpfGroups(len(groups), _p(gp), _p(gn))
+        src = np.ascontiguousarray(sources, dtype=np.uint32)
+        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
+        solved = ctypes.c_uint64()
+        if cap is None:
+            _check(self._lib.openr_spf_whatif_maint_routes(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
+                                                           ctypes.byref(gs), _p(changed), None,
+                                                           ctypes.byref(solved)))
+            cap = int(changed.sum(dtype=np.uint64))
+        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
+        group = np.zeros(max(cap, 1), dtype=np.uint32)
+        metric = np.zeros(max(cap, 1), dtype=np.uint64)
+        nh = np.zeros((max(cap, 1), nb), dtype=np.uint8)
+        n_best = np.zeros(max(cap, 1), dtype=np.uint32)
+        d = WhatifRoutes(_p(ptr), _p(group), _p(metric), _p(nh), _p(n_best), cap, nb)
+        _check(self._lib.openr_spf_whatif_maint_routes(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
+                                                       ctypes.byref(gs), _p(changed), ctypes.byref(d),
+                                                       ctypes.byref(solved)))
+        del keep
+        k = int(ptr[-1])
+        return changed, ptr, group[:k], metric[:k], nh[:k], n_best[:k], int(solved.value)
+
+    def whatif_maint_routes_device(self, d_node_ptr: int, d_nodes: int, d_link_ptr: int, d_links: int,
+                                   d_edge_ptr: int, d_edges: int, d_metrics: int, n_events: int, n_nodes: int,
+                                   n_links: int, n_edges: int, d_sources: int, n_sources: int, d_group_ptr: int,
+                                   d_group_nodes: int, n_groups: int, n_group_nodes: int, d_changed: int,
+                                   d_ptr: int, d_group: int, d_metric: int, d_nh: int, d_n_best: int, cap: int,
+                                   nh_bytes: int, use_link_metric: bool = True, stream: int = 0,
+                                   device_index: int = 0, allow_overflow: bool = False) -> Tuple[int, int]:
+        """Device-pointer form: (total entries, solved); outputs as whatif_routes_device."""
+        vp = ctypes.c_void_p
+        total = ctypes.c_uint64()
+        solved = ctypes.c_uint64()
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        rc = self._lib.openr_spf_whatif_maint_routes_device(
             self._ctx, device_index, vp(d_node_ptr or None), vp(d_nodes or None), vp(d_link_ptr or None),
             vp(d_links or None), vp(d_edge_ptr or None), vp(d_edges or None), vp(d_metrics or None), n_events, n_nodes,
             n_links, n_edges, vp(d_sources), n_sources, flags, vp(d_group_ptr or None), vp(d_group_nodes or None),

@@ -608,6 +608,29 @@ def restore_events(g: CsrGraph, node_sets: Optional[Iterable[Iterable[int]]] = N
     return nodes, links, out_e, out_m
 
 
+def maint_events(g: CsrGraph, node_sets: Optional[Iterable[Iterable[int]]] = None,
+                 link_sets: Optional[Iterable[Iterable[int]]] = None,
+                 edge_sets: Optional[Iterable[Iterable[int]]] = None,
+                 metric_sets: Optional[Iterable[Iterable[int]]] = None):
+    """Maintenance events for ``SpfEngine.whatif_maint`` / ``whatif_maint_routes``: per event
+    the nodes that get the overload bit, the links taken out of service and the directed CSR
+    edges with their new, higher metric. Any kind may be None (no entry of it in any event);
+    the kinds given must have one entry per event. Nodes and links are validated,
+    de-duplicated and sorted as ``drain_events`` does; edge entries are handled as
+    ``metric_events`` does (new metric in [current metric, 2^31 - 1], an edge listed twice
+    keeps the larger metric). Returns (node_sets, link_sets, edge_sets, metric_sets), a kind
+    that was None staying None."""
+    if (edge_sets is None) != (metric_sets is None):
+        raise ValueError("edge_sets and metric_sets go together")
+    nodes = prefix_groups(g, node_sets) if node_sets is not None else None
+    links = srlg_sets(g, link_sets) if link_sets is not None else None
+    out_e, out_m = metric_events(g, edge_sets, metric_sets) if edge_sets is not None else (None, None)
+    counts = {len(x) for x in (nodes, links, out_e) if x is not None}
+    if len(counts) > 1:
+        raise ValueError(f"the kinds of a maintenance event list differ in length: {sorted(counts)}")
+    return nodes, links, out_e, out_m
+
+
 def prefix_groups(g: CsrGraph, groups: Iterable[Iterable[int]]) -> List[List[int]]:
     """Caller-given prefix groups (the advertisers of each prefix) as a group table for
     ``SpfEngine.routes`` / ``whatif_routes``: every group validated (node ids in
