@@ -151,7 +151,10 @@ const char* openr_spf_build_id(void);
 const char* openr_spf_last_error(void);
 /* Diagnostics: "name;name;..." of the kernels the calling thread's last solve call
    (openr_spf_solve*, _solve_device) enqueued, re-run launches included (tests assert
-   which kernel a configuration runs). */
+   which kernel a configuration runs); every what-if, routes and LFA call starts a new
+   trace too. The general-metric kernels and the link what-if repairs also note their
+   distance type: "fringe_kernel<u64>" / "rounds_kernel<u32>" after the plain name,
+   "whatif_group<u16|u32|u64[,lds]>" (",lds": graph staged in LDS), "whatif_incr<u32|u64>". */
 const char* openr_spf_last_kernels(void);
 void openr_spf_limits(openr_spf_limits_t* out);
 

@@ -3824,6 +3824,7 @@ int openr_spf_take_status(openr_spf_ctx* ctx, int device_index, uint32_t* out_st
 
 int openr_spf_whatif(openr_spf_ctx* ctx, const uint32_t* links, uint32_t n_links, const uint32_t* sources,
                      uint32_t n_sources, uint32_t flags, uint32_t* changed, uint64_t* out_solved) {
+  clear_launch_trace();
   WhatifUnits hu;
   hu.links = links;
   hu.n = n_links;
@@ -3841,6 +3842,7 @@ int openr_spf_whatif_sets(openr_spf_ctx* ctx, const uint32_t* set_ptr, const uin
 int openr_spf_whatif_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_links, uint32_t n_links,
                             const uint32_t* d_sources, uint32_t n_sources, uint32_t flags, uint32_t* d_changed,
                             void* stream, uint64_t* out_solved) {
+  clear_launch_trace();
   WhatifUnits un;
   un.links = d_links;
   un.n = n_links;
@@ -3861,6 +3863,7 @@ int openr_spf_whatif_delta_device(openr_spf_ctx* ctx, int device_index, const ui
                                   const uint32_t* d_sources, uint32_t n_sources, uint32_t flags, uint32_t* d_changed,
                                   uint64_t* d_ptr, uint32_t* d_node, uint64_t* d_dist, uint8_t* d_nh, uint64_t cap,
                                   uint32_t nh_bytes, void* stream, uint64_t* out_total, uint64_t* out_solved) {
+  clear_launch_trace();
   WhatifUnits un;
   un.links = d_links;
   un.n = n_links;
@@ -3884,6 +3887,7 @@ int openr_spf_whatif_sets_delta_device(openr_spf_ctx* ctx, int device_index, con
 int openr_spf_whatif_delta(openr_spf_ctx* ctx, const uint32_t* links, uint32_t n_links, const uint32_t* sources,
                            uint32_t n_sources, uint32_t flags, uint32_t* changed, openr_spf_whatif_delta_t* delta,
                            uint64_t* out_solved) {
+  clear_launch_trace();
   WhatifUnits hu;
   hu.links = links;
   hu.n = n_links;

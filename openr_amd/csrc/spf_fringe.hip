@@ -235,6 +235,7 @@ hipError_t launch_fringe_t(const DevGraph& g, const SolveArgs& a, uint32_t delta
                                        (int)lds);
   if (err != hipSuccess) return err;
   note_launch("fringe_kernel");
+  note_launch(sizeof(D) == 8 ? "fringe_kernel<u64>" : "fringe_kernel<u32>");  // LaunchInfo::kernel
   hipLaunchKernelGGL(k, dim3(grid), dim3(kWave), lds, s, g, a, delta, (uint32_t)has_ign, ctr);
   return hipGetLastError();
 }

@@ -512,6 +512,7 @@ hipError_t launch_rounds_b(const DevGraph& g, const SolveArgs& a, uint32_t lds, 
                                        (int)lds);
   if (err != hipSuccess) return err;
   note_launch("rounds_kernel");
+  note_launch(sizeof(D) == 8 ? "rounds_kernel<u64>" : "rounds_kernel<u32>");  // LaunchInfo::kernel
   hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), lds, s, g, a, (uint32_t)has_ign, ctr);
   return hipGetLastError();
 }

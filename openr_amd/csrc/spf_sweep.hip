@@ -1511,6 +1511,7 @@ hipError_t launch_whatif_incr(const DevGraph& g, const uint32_t* wsrc, const uin
   hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)lds);
   if (err != hipSuccess) return err;
+  note_launch(dist64 ? "whatif_incr<u64>" : "whatif_incr<u32>");
   hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, s, g, wsrc, wlink, wunit, count, n_src, base_dist, base_nh, nb,
                      (uint32_t)unit_cost, changed, ctr);
   return hipGetLastError();
@@ -1641,6 +1642,10 @@ hipError_t launch_whatif_group(const DevGraph& g, const uint32_t* links, uint32_
                        ovf_src, ovf_link,                                                                      \
                        ovf_unit, ctr, prof, dl);                                                               \
   } while (0)
+  // the distance type and the graph variant, for tests of the tier rules above
+  note_launch(d16 ? (lg ? "whatif_group<u16,lds>" : "whatif_group<u16>")
+                  : dist64 ? (lg ? "whatif_group<u64,lds>" : "whatif_group<u64>")
+                           : (lg ? "whatif_group<u32,lds>" : "whatif_group<u32>"));
   if (d16) {
     if (lg) OPENR_GRP_LAUNCH(uint16_t, true);
     else OPENR_GRP_LAUNCH(uint16_t, false);

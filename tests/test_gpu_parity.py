@@ -537,7 +537,8 @@ def whatif_oracle(g, links, sources, use_metric=True):
 def whatif_mode(request, monkeypatch):
     """What-if units repaired from LDS-staged base rows per (source, link chunk) workgroup
     (default: graph read from global memory, u16 distances when they fit; or the graph
-    staged in LDS too; or u32 / u64 distances), per-unit incremental repair, or full
+    staged in LDS too; or u32 distances forced where u16 would fit; no mode reaches u64, the
+    graph's V * w_max alone does: tests/test_gpu_dist_tiers.py), per-unit incremental repair, or full
     re-solves. group-cap: 3 dirty slots per wave, so most units are re-solved; group-cap1:
     1 slot, so nearly every affected unit takes the seeded re-solve (the rounds kernel
     starting from the base rows); group-items: 1 item per workgroup and 60 % of each
