@@ -151,7 +151,7 @@ const char* openr_spf_build_id(void);
 const char* openr_spf_last_error(void);
 /* Diagnostics: "name;name;..." of the kernels the calling thread's last solve call
    (openr_spf_solve*, _solve_device) enqueued, re-run launches included (tests assert
-   which kernel a configuration runs); every what-if, routes and LFA call starts a new
+   which kernel a configuration runs); every what-if, routes, LFA and KSP2 call starts a new
    trace too. The general-metric kernels and the link what-if repairs also note their
    distance type: "fringe_kernel<u64>" / "rounds_kernel<u32>" after the plain name,
    "whatif_group<u16|u32|u64[,lds]>" (",lds": graph staged in LDS), "whatif_incr<u32|u64>". */
@@ -974,7 +974,12 @@ int openr_spf_whatif_maint_routes_device(openr_spf_ctx* ctx, int device_index, c
    reference's order; tokens past a row's used prefix are left unspecified. k = 2 ignores the links of the k = 1 paths. Link metrics are
    used (getKthPaths calls getSpfResult(src, true) / runSpf(src, true, ignore)). A pair
    whose paths exceed tok_cap tokens (or 255 hops) gets n_paths = 0xFFFFFFFF and the
-   call returns OPENR_SPF_E2BIG after filling the others. */
+   call returns OPENR_SPF_E2BIG after filling the others. So does a pair whose trace outgrows
+   the tracer's arena: the depth-first search keeps the still untried pathLinks of every node
+   on its stack, 1024 entries at most (a 33-hop path through layers of 32 nodes, each linked
+   to the whole next layer, needs 1025). A row is marked on its own: tok2 may be marked where
+   tok1 is not (the k = 2 paths are longer). Where tok1 is marked the k = 1 links are unknown,
+   and the pair's tok2 row is marked as well. */
 int openr_spf_ksp2(openr_spf_ctx* ctx, const uint32_t* src, const uint32_t* dst, uint32_t n_pairs,
                    uint32_t tok_cap, uint32_t* tok1, uint32_t* tok2);
 

@@ -948,7 +948,8 @@ constexpr size_t kKspChunkBytes = size_t(8) << 30;  // second-SPF rows + ignore 
 // of every listed source (the reference's memoized getSpfResult), then per chunk of
 // pairs: k = 1 trace on the base rows (its links become the pair's ignore set), the
 // second SPF with that ignore set (runSpf(src, true, ignore)), the k = 2 trace.
-// Sets *overflow when a pair's paths exceed tok_cap tokens or kKspMaxDepth hops.
+// Sets *overflow when a pair's paths exceed tok_cap tokens or kKspMaxDepth - 1 hops, or its
+// trace kKspArena pathLinks on the DFS stack.
 hipError_t ksp2_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, const Plan& ign_plan,
                           const uint32_t* d_sources, uint32_t n_src, const uint32_t* d_prow, const uint32_t* d_pdst,
                           uint32_t n_pairs, uint32_t tok_cap, uint32_t* d_tok1, uint32_t* d_tok2, hipStream_t s,
@@ -1071,8 +1072,9 @@ hipError_t ksp2_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, 
   const uint32_t nst = ksp_stats_count();
   unsigned long long* kst = nullptr;
   if (prof_enabled()) {
-    OPENR_TRY(hipMallocAsync(reinterpret_cast<void**>(&kst), 2 * nst * sizeof(unsigned long long), s));
-    OPENR_TRY(hipMemsetAsync(kst, 0, 2 * nst * sizeof(unsigned long long), s));
+    // ... and, after them, the pairs the repair kernel kept / handed to the forward solve
+    OPENR_TRY(hipMallocAsync(reinterpret_cast<void**>(&kst), (2 * nst + 2) * sizeof(unsigned long long), s));
+    OPENR_TRY(hipMemsetAsync(kst, 0, (2 * nst + 2) * sizeof(unsigned long long), s));
   }
   for (uint32_t first = 0; first < n_pairs; first += chunk) {
     const uint32_t m = std::min(chunk, n_pairs - first);
@@ -1133,6 +1135,7 @@ hipError_t ksp2_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, 
                                   b.ign_links, d.kbase.p, tl_off, base_plan.cost, b.lvl16, b.lvl_tag << b.lvl_shift,
                                   (1u << b.lvl_shift) - 1u, rmode, rlist3, rpart3 + kCls8, d.kretry.p + 6,
                                   d.num_cus, ls));
+      if (kst) OPENR_TRY(launch_ksp_repair_count(rmode, keep, keep_count, m, kst + 2 * nst, d.num_cus, ls));
       b.perm = rlist3;  // the pairs it handed back: the forward solve
       b.part = rpart3;
     }
@@ -1151,7 +1154,7 @@ hipError_t ksp2_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, 
                                repair ? rmode : nullptr));
   }
   if (kst) {
-    std::vector<unsigned long long> h(2 * nst);
+    std::vector<unsigned long long> h(2 * nst + 2);
     OPENR_TRY(hipMemcpyAsync(h.data(), kst, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     OPENR_TRY(hipStreamSynchronize(s));
     OPENR_TRY(hipFree(kst));
@@ -1160,6 +1163,8 @@ hipError_t ksp2_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, 
       for (uint32_t i = 0; i < nst; ++i) std::fprintf(stderr, " %llu", h[k * nst + i]);
       std::fprintf(stderr, "\n");
     }
+    // second SPFs by the way they were solved, summed over the chunks (both 0: no repair launch)
+    std::fprintf(stderr, "ksp_repair kept=%llu forward=%llu\n", h[2 * nst], h[2 * nst + 1]);
   }
   uint32_t status = 0;
   OPENR_TRY(hipMemcpyAsync(&status, d.kstatus.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -4694,6 +4699,7 @@ int openr_spf_whatif_restore_lfa_device(openr_spf_ctx* ctx, int device_index, co
 
 int openr_spf_ksp2(openr_spf_ctx* ctx, const uint32_t* src, const uint32_t* dst, uint32_t n_pairs,
                    uint32_t tok_cap, uint32_t* tok1, uint32_t* tok2) {
+  clear_launch_trace();
   if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
   if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
   if (n_pairs && (!src || !dst || !tok1 || !tok2)) return fail(OPENR_SPF_EINVAL, "null argument");
@@ -4738,14 +4744,17 @@ int openr_spf_ksp2(openr_spf_ctx* ctx, const uint32_t* src, const uint32_t* dst,
   ctx->stats.last_batch_ms =
       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (overflow)
-    return fail(OPENR_SPF_E2BIG, "a pair's paths exceed tok_cap=%u tokens or %u hops (marked 0xFFFFFFFF)", tok_cap,
-                kKspMaxDepth - 1u);
+    return fail(OPENR_SPF_E2BIG,
+                "a pair's paths exceed tok_cap=%u tokens or %u hops, or its trace more than %u pathLinks on the DFS "
+                "stack (marked 0xFFFFFFFF)",
+                tok_cap, kKspMaxDepth - 1u, kKspArena);
   return OPENR_SPF_OK;
 }
 
 int openr_spf_ksp2_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_sources, uint32_t n_sources,
                           const uint32_t* d_pair_row, const uint32_t* d_pair_dst, uint32_t n_pairs, uint32_t tok_cap,
                           uint32_t* d_tok1, uint32_t* d_tok2, void* stream) {
+  clear_launch_trace();
   if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
   if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
   if (device_index < 0 || device_index >= (int)ctx->devs.size())
@@ -4769,8 +4778,10 @@ int openr_spf_ksp2_device(openr_spf_ctx* ctx, int device_index, const uint32_t* 
   ctx->stats.spf_runs += (uint64_t)n_sources + n_pairs;
   ctx->stats.batches += 1;
   if (overflow)
-    return fail(OPENR_SPF_E2BIG, "a pair's paths exceed tok_cap=%u tokens or %u hops (marked 0xFFFFFFFF)", tok_cap,
-                kKspMaxDepth - 1u);
+    return fail(OPENR_SPF_E2BIG,
+                "a pair's paths exceed tok_cap=%u tokens or %u hops, or its trace more than %u pathLinks on the DFS "
+                "stack (marked 0xFFFFFFFF)",
+                tok_cap, kKspMaxDepth - 1u, kKspArena);
   return OPENR_SPF_OK;
 }
 

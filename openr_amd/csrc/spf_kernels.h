@@ -748,6 +748,10 @@ hipError_t launch_ksp_repair(const DevGraph& g, const uint32_t* srcs, const uint
                              const uint32_t* tl_off, uint64_t cost, uint16_t* rows16, uint32_t ltag, uint32_t lmask,
                              uint32_t* mode, uint32_t* retry_list, uint32_t* retry_count, uint32_t* work_ctr,
                              int num_cus, hipStream_t s);
+// OPENR_SPF_PROF only: after launch_ksp_repair, out[0] += the listed pairs it kept (mode 0),
+// out[1] += those it handed to the forward solve (mode 1)
+hipError_t launch_ksp_repair_count(const uint32_t* mode, const uint32_t* list, const uint32_t* list_count, uint32_t n,
+                                   unsigned long long* out, int num_cus, hipStream_t s);
 // The k = 1 trace's pathLinks lists: for base row j (source sources[j], distances rows[j]),
 // off[j][0 .. V] (V + 1 u32) and ent[j][off[v] .. off[v + 1]) = node v's tight in-edges in
 // rank order as {u->v edge, link | u << 16} (ent holds E entries per source). Needs

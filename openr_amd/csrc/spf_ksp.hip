@@ -1247,7 +1247,31 @@ __global__ __launch_bounds__(BLOCK) void ksp_repair_kernel(DevGraph g, const uin
   }
 }
 
+// OPENR_SPF_PROF launches only: out[0] += the listed pairs ksp_repair_kernel kept (mode 0),
+// out[1] += those it handed to the forward solve (mode 1)
+__global__ __launch_bounds__(256) void ksp_repair_count(const uint32_t* mode, const uint32_t* list,
+                                                        const uint32_t* list_count, uint32_t n,
+                                                        unsigned long long* out) {
+  const uint32_t units = list ? *list_count : n;
+  uint32_t kept = 0, fwd = 0;
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < units; i += gridDim.x * 256u) {
+    const uint32_t k = list ? list[i] : i;
+    if (k < n) (mode[k] ? fwd : kept) += 1u;
+  }
+  if (kept) atomicAdd(&out[0], (unsigned long long)kept);
+  if (fwd) atomicAdd(&out[1], (unsigned long long)fwd);
+}
+
 }  // namespace
+
+hipError_t launch_ksp_repair_count(const uint32_t* mode, const uint32_t* list, const uint32_t* list_count, uint32_t n,
+                                   unsigned long long* out, int num_cus, hipStream_t s) {
+  if (!n) return hipSuccess;
+  if (!mode || !out) return hipErrorInvalidValue;
+  const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>((n + 255u) / 256u, (uint32_t)num_cus * 8u));
+  hipLaunchKernelGGL(ksp_repair_count, dim3(grid), dim3(256), 0, s, mode, list, list_count, n, out);
+  return hipGetLastError();
+}
 
 // A u16 copy of the pair's distance row in LDS was measured slower on the fabric (fewer
 // wavefronts per CU, rounds 2-3) and is not taken; the layout keeps the slot at size 0.
