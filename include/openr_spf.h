@@ -914,9 +914,8 @@ int openr_spf_whatif_restore_lfa_device(openr_spf_ctx* ctx, int device_index, co
    event) or above 2^31 - 1, or n_events * n_sources > 2^32 - 1; OPENR_SPF_ENOTSUP when the
    base SPF needs the exact-order kernel (as openr_spf_whatif_drain; the hop-count form of such
    a graph is served); OPENR_SPF_E2BIG when a unit's state does not fit LDS. Not covered: events
-   that mix worsening with restoring changes, exact-order base plans, the C++ LinkState mirror,
-   and a loop-free-alternate form of this sweep (openr_spf_whatif_drain_lfa and its siblings
-   take one family's events each). */
+   that mix worsening with restoring changes, exact-order base plans and the C++ LinkState
+   mirror. Loop-free alternates under a maintenance event are openr_spf_whatif_maint_lfa below. */
 typedef struct {
   uint32_t n_events;
   const uint32_t* node_ptr;  /* [n_events + 1] */
@@ -966,6 +965,53 @@ int openr_spf_whatif_maint_routes_device(openr_spf_ctx* ctx, int device_index, c
                                          uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
                                          uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes, void* stream,
                                          uint64_t* out_total, uint64_t* out_solved);
+
+/* Loop-free alternates under a maintenance event: which prefixes stop being protected while
+   the window is open. Events are those of openr_spf_whatif_maint, groups and outputs those of
+   openr_spf_whatif_lfa. For event i = (N_i, K_i, raises), source j (node s) and group k the
+   entry (metric', nh', alt') is what openr_spf_lfa_routes returns for (s, k) on the graph
+   patched by the whole event; it is listed iff it differs from the no-event entry.
+   Overlaying the answers of openr_spf_whatif_drain_lfa for (N_i, K_i) and of
+   openr_spf_whatif_metric_lfa for the raises does not give this answer.
+     - the reference's LFA loop (Decision.cpp:1169-1204) skips a link iff it is not up, reads
+       the neighbour's own SPF row for toMe and for the members, and reads shortestMetric. It
+       never reads the metric of the link s-n. So neither a raise nor an overload bit changes
+       a tested status: a neighbour n of s is tested iff some link s-n is up and not in K_i,
+       as under a drain event.
+     - a raise acts through rows only: one on s -> n shows in the source's rows, one on n -> s
+       in the rows of n (toMe = dist_n(s) moves). The rows are those of
+       openr_spf_whatif_maint's unit (i, n), in which n expands because it is the source.
+     - the closure is the drain's: the sources as given, then their up neighbours that are no
+       source, ascending; *out_solved is what openr_spf_whatif_maint reports for the same
+       events over that list (added to stats.spf_runs; a rerun of the sweep on scratch
+       overflow counts once).
+   Without OPENR_SPF_USE_LINK_METRIC the raises are ignored and the answer is that of
+   openr_spf_whatif_drain_lfa for (N_i, K_i), bit for bit; the sweep still runs.
+   Errors: events as openr_spf_whatif_maint checks them (OPENR_SPF_EINVAL for a decrease,
+   OPENR_SPF_ENOTSUP for an exact-order base plan under link metric), groups and nh_bytes as
+   openr_spf_whatif_lfa; a graph whose repair unit does not fit LDS is OPENR_SPF_ENOTSUP here.
+   OPENR_SPF_E2BIG means sum(changed) > cap and nothing else. Events are split in contiguous
+   blocks across the context's devices; each unit's entries are sorted by group. Not covered:
+   per-alternate metrics, perDestination = true, multi-area, chunking of the sources. */
+int openr_spf_whatif_maint_lfa(openr_spf_ctx* ctx, const openr_spf_maint_events_t* events, const uint32_t* sources,
+                               uint32_t n_sources, uint32_t flags, const openr_spf_groups_t* groups,
+                               uint32_t* changed, uint32_t* unprotected, uint32_t* lost_backup,
+                               openr_spf_whatif_lfa_t* delta, uint64_t* out_solved);
+
+/* Device-buffer form: events as openr_spf_whatif_maint_device (nothing is validated, every
+   slice is clamped, bad ids and entries whose metric is not in (current, 2^31 - 1] are
+   skipped), groups and outputs as openr_spf_whatif_lfa_device (d_ptr NULL: counts only;
+   entries in the kernel's order). Synchronizes `stream`. */
+int openr_spf_whatif_maint_lfa_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
+                                      const uint32_t* d_nodes, const uint32_t* d_link_ptr, const uint32_t* d_links,
+                                      const uint32_t* d_edge_ptr, const uint32_t* d_edges, const uint32_t* d_metrics,
+                                      uint32_t n_events, uint32_t n_nodes, uint32_t n_links, uint32_t n_edges,
+                                      const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                                      const uint32_t* d_group_ptr, const uint32_t* d_group_nodes, uint32_t n_groups,
+                                      uint32_t n_group_nodes, uint32_t* d_changed, uint32_t* d_unprotected,
+                                      uint32_t* d_lost_backup, uint64_t* d_ptr, uint32_t* d_group,
+                                      uint64_t* d_metric, uint8_t* d_nh, uint8_t* d_alt, uint64_t cap,
+                                      uint32_t nh_bytes, void* stream, uint64_t* out_total, uint64_t* out_solved);
 
 /* LinkState::getKthPaths(src[i], dst[i], 1) and (.., 2) (LinkState.cpp:762-791, with
    traceOnePath :398-419) for a batch of pairs, traced on the device. Per pair, tok1 /

@@ -2609,7 +2609,9 @@ struct WlfaOut {
 // events of that family, the node sweep is the family's repair sweep and the passes are those
 // of spf_elfa.hip. A restore widens the closure to every neighbour of a source and gives the
 // pass a table of its own over it; the hop-count form of a metric sweep solves the base rows
-// only (nothing moves: every unit gets its source's base unprotected count).
+// only (nothing moves: every unit gets its source's base unprotected count). kElfaMaint: the
+// node sweep is the maintenance sweep (whatif_units_on_device goes by the unit kind), closure,
+// table and pass are the drain's; its hop-count form is not idle (N_i and K_i still act).
 int whatif_lfa_on_device(openr_spf_ctx* ctx, Device& d, const WhatifUnits& un, const uint32_t* d_sources,
                          uint32_t n_src, uint32_t flags, const DevGroups& gr, const WlfaOut& out, hipStream_t s,
                          uint64_t* total, uint64_t* solved_out, int fam = -1) {
@@ -4528,7 +4530,7 @@ int openr_spf_whatif_lfa_device(openr_spf_ctx* ctx, int device_index, const uint
   return rc;
 }
 
-// ---- loop-free alternates under drain, metric and restore events (spf_elfa.hip) ---------------
+// ---- loop-free alternates under drain, metric, restore and maintenance events (spf_elfa.hip) --
 
 // The family's capacity check for a call whose only E2BIG is "sum(changed) > cap": a graph
 // whose repair unit does not fit LDS is not supported by these calls.
@@ -4693,6 +4695,48 @@ int openr_spf_whatif_restore_lfa_device(openr_spf_ctx* ctx, int device_index, co
                           restore_units(d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics,
                                         n_events, n_nodes, n_links, n_edges),
                           kElfaRestore, d_sources, n_sources, flags, d_group_ptr, d_group_nodes, n_groups,
+                          n_group_nodes, d_changed, d_unprotected, d_lost_backup, d_ptr, d_group, d_metric, d_nh,
+                          d_alt, cap, nh_bytes, stream, out_total, out_solved);
+}
+
+// Loop-free alternates under a maintenance event: the maintenance sweep's rows under the drain's
+// pass (kElfaMaint; the argument is at openr_spf_whatif_maint_lfa and in spf_elfa.hip's header).
+int openr_spf_whatif_maint_lfa(openr_spf_ctx* ctx, const openr_spf_maint_events_t* events, const uint32_t* sources,
+                               uint32_t n_sources, uint32_t flags, const openr_spf_groups_t* groups,
+                               uint32_t* changed, uint32_t* unprotected, uint32_t* lost_backup,
+                               openr_spf_whatif_lfa_t* delta, uint64_t* out_solved) {
+  if (out_solved) *out_solved = 0;
+  WhatifUnits hu;
+  const int rc = event_lfa_check(check_maint_host(ctx, events, sources, n_sources, flags, changed, &hu));
+  if (rc) return rc;
+  return whatif_lfa_host(ctx, hu, sources, n_sources, flags, groups, changed, unprotected, lost_backup, delta,
+                         out_solved, kElfaMaint);
+}
+
+int openr_spf_whatif_maint_lfa_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
+                                      const uint32_t* d_nodes, const uint32_t* d_link_ptr, const uint32_t* d_links,
+                                      const uint32_t* d_edge_ptr, const uint32_t* d_edges, const uint32_t* d_metrics,
+                                      uint32_t n_events, uint32_t n_nodes, uint32_t n_links, uint32_t n_edges,
+                                      const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                                      const uint32_t* d_group_ptr, const uint32_t* d_group_nodes, uint32_t n_groups,
+                                      uint32_t n_group_nodes, uint32_t* d_changed, uint32_t* d_unprotected,
+                                      uint32_t* d_lost_backup, uint64_t* d_ptr, uint32_t* d_group,
+                                      uint64_t* d_metric, uint8_t* d_nh, uint8_t* d_alt, uint64_t cap,
+                                      uint32_t nh_bytes, void* stream, uint64_t* out_total, uint64_t* out_solved) {
+  clear_launch_trace();
+  if (out_total) *out_total = 0;
+  if (out_solved) *out_solved = 0;
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  if (n_events && (!d_node_ptr || (n_nodes && !d_nodes) || (d_link_ptr && n_links && !d_links) ||
+                   (d_edge_ptr && n_edges && (!d_edges || !d_metrics))))
+    return fail(OPENR_SPF_EINVAL, "null node_ptr, nodes, links, edges or metrics");
+  const int rc = event_lfa_check(check_maint(ctx, flags, n_events, n_sources));
+  if (rc) return rc;
+  return event_lfa_device(ctx, device_index,
+                          maint_units(d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics,
+                                      n_events, n_nodes, n_links, n_edges),
+                          kElfaMaint, d_sources, n_sources, flags, d_group_ptr, d_group_nodes, n_groups,
                           n_group_nodes, d_changed, d_unprotected, d_lost_backup, d_ptr, d_group, d_metric, d_nh,
                           d_alt, cap, nh_bytes, stream, out_total, out_solved);
 }

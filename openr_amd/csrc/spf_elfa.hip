@@ -1,5 +1,5 @@
-// spf_elfa.hip — loop-free alternates under drain, metric and restore events
-// (openr_spf_whatif_drain_lfa*, _metric_lfa*, _restore_lfa*): the LFA rule of spf_lfa.hip
+// spf_elfa.hip — loop-free alternates under drain, metric, restore and maintenance events
+// (openr_spf_whatif_drain_lfa*, _metric_lfa*, _restore_lfa*, _maint_lfa*): the LFA rule of spf_lfa.hip
 // resolved per event of an event sweep, as spf_wlfa.hip resolves it per failure set.
 //
 // For event i, source j (node s) and group k the answer is the LFA RIB entry (metric', nh',
@@ -22,6 +22,11 @@
 //            with restore_filter / restore_repair). A status can only be gained, and the
 //            closure holds every neighbour of a source for that reason (launch_elfa_rows,
 //            launch_elfa_table: the table of neighbours with a closure row).
+//   maintenance (kElfaMaint, openr_spf_whatif_maint_lfa*): the drain policy, unchanged. The
+//            loop never reads the metric of a link s-n, so a raise changes no tested status: a
+//            raise on s -> n shows in the source's delta, a raise on n -> s as node s in the
+//            delta of unit (i, n) (toMe moved), both rows of the maintenance sweep. The launchers
+//            send the family to the drain instantiations; no kernel is added for it.
 //
 // elfa_base: per source, the base `unprotected` count (as wlfa_base).
 // elfa_mark<FAM>: a thread per unit. A unit can differ from its base only if the source's
@@ -573,12 +578,14 @@ hipError_t launch_elfa_mark(const DevGraph& g, const ElfaPass& p, int fam, int n
   const uint32_t cap = (uint32_t)num_cus * 8u;
   hipLaunchKernelGGL(elfa_base, dim3(std::max(1u, std::min(p.w.n_src, cap))), dim3(256), 0, s, p.w);
   const dim3 grid(capped_grid((units + 255u) / 256u, num_cus, 8u));
-  if (fam == kElfaDrain)
+  if (fam == kElfaDrain || fam == kElfaMaint)  // a maintenance event's N_i and K_i are a drain's
     hipLaunchKernelGGL(elfa_mark<kElfaDrain>, grid, dim3(256), 0, s, g, p);
   else if (fam == kElfaMetric)
     hipLaunchKernelGGL(elfa_mark<kElfaMetric>, grid, dim3(256), 0, s, g, p);
-  else
+  else if (fam == kElfaRestore)
     hipLaunchKernelGGL(elfa_mark<kElfaRestore>, grid, dim3(256), 0, s, g, p);
+  else
+    return hipErrorInvalidValue;
   note_launch("elfa_mark");
   return hipGetLastError();
 }
@@ -600,13 +607,17 @@ hipError_t launch_elfa(const DevGraph& g, const ElfaPass& pass, const WlfaLayout
     else                                                                                 \
       hipLaunchKernelGGL((elfa_kernel<F, false>), grid, block, l.lds_bytes, s, g, p);    \
   } while (0)
-  if (fam == kElfaDrain)
+  bool known = true;
+  if (fam == kElfaDrain || fam == kElfaMaint)  // a maintenance event's N_i and K_i are a drain's
     OPENR_ELFA_LAUNCH(kElfaDrain);
   else if (fam == kElfaMetric)
     OPENR_ELFA_LAUNCH(kElfaMetric);
-  else
+  else if (fam == kElfaRestore)
     OPENR_ELFA_LAUNCH(kElfaRestore);
+  else
+    known = false;
 #undef OPENR_ELFA_LAUNCH
+  if (!known) return hipErrorInvalidValue;
   note_launch(emit ? "elfa_emit" : "elfa_count");
   return hipGetLastError();
 }

@@ -634,7 +634,7 @@ hipError_t launch_maint_filter(const DevGraph& g, const MaintPass& p, int num_cu
 hipError_t launch_maint_repair(const DevGraph& g, const MaintPass& p, uint32_t count, bool rerun, int num_cus,
                                hipStream_t s);
 
-// Loop-free alternates under drain, metric and restore events (spf_elfa.hip): the pass of
+// Loop-free alternates under drain, metric, restore and maintenance events (spf_elfa.hip): the pass of
 // spf_wlfa.hip over the node deltas of an event sweep (events x closure rows). The rule is in
 // that file's header and at openr_spf_whatif_drain_lfa.
 //   w    the pass as spf_wlfa.hip reads it; n_sets = events, set_ptr / set_links = the links
@@ -643,7 +643,10 @@ hipError_t launch_maint_repair(const DevGraph& g, const MaintPass& p, uint32_t c
 //        the base table)
 //   ev   restore only: the event CSRs as the restore sweep takes them (and unit_cost)
 //   idle the hop-count form of a metric sweep: nothing moves, the mark pass lists no unit
-enum ElfaFamily : int { kElfaDrain = 0, kElfaMetric = 1, kElfaRestore = 2 };
+// kElfaMaint (openr_spf_whatif_maint_lfa): the node sweep is the maintenance sweep, the pass is
+// the drain's. The LFA loop never reads the metric of a link s-n, so a raise changes no tested
+// status and acts through the rows of the sweep alone; N_i and K_i act as in a drain event.
+enum ElfaFamily : int { kElfaDrain = 0, kElfaMetric = 1, kElfaRestore = 2, kElfaMaint = 3 };
 struct ElfaPass {
   WlfaPass w;
   RestorePass ev;

@@ -41,9 +41,11 @@
 // when R is walked, not when it is built: build fills the three bitmaps side by side and the
 // policy holds no barrier.
 //
-// Not covered: loop-free alternates under a maintenance event (spf_elfa.hip would need a fourth
-// family whose LFA loop knows both K_i and the raised source-to-neighbour metrics), events that
-// mix worsening with restoring changes, exact-order base plans, the C++ LinkState mirror.
+// Loop-free alternates under a maintenance event (openr_spf_whatif_maint_lfa*) run this sweep
+// over the closure of the sources and hand its rows to the drain pass of spf_elfa.hip: the LFA
+// loop never reads the metric of a link s-n, so the raises act through these rows alone.
+// Not covered: events that mix worsening with restoring changes, exact-order base plans, the
+// C++ LinkState mirror.
 //
 // Uniformity: the policy's loops (over an event's nodes, links and entries, bitmap words, bits
 // and rows, the binary search) have per-lane trip counts and hold no barrier and no wave

@@ -80,6 +80,8 @@ EXPORTS = (
     "openr_spf_whatif_maint_device",
     "openr_spf_whatif_maint_routes",
     "openr_spf_whatif_maint_routes_device",
+    "openr_spf_whatif_maint_lfa",
+    "openr_spf_whatif_maint_lfa_device",
     "openr_spf_ksp2",
     "openr_spf_ksp2_device",
     "openr_spf_host_alloc",
@@ -332,6 +334,8 @@ def load_library():
     l.openr_spf_whatif_restore_lfa.argtypes = [vp, P(RestoreEvents)] + lfa_host
     l.openr_spf_whatif_restore_lfa_device.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32,
                                                       u32] + lfa_dev
+    l.openr_spf_whatif_maint_lfa.argtypes = [vp, P(MaintEvents)] + lfa_host
+    l.openr_spf_whatif_maint_lfa_device.argtypes = l.openr_spf_whatif_restore_lfa_device.argtypes
     l.openr_spf_ksp2.argtypes = [vp, vp, vp, u32, u32, vp, vp]
     l.openr_spf_ksp2_device.argtypes = [vp, ctypes.c_int, vp, u32, vp, vp, u32, u32, vp, vp, vp]
     l.openr_spf_host_alloc.argtypes = [ctypes.c_size_t, P(vp)]
@@ -1300,7 +1304,7 @@ class SpfEngine:
             _check(rc)
         return int(total.value), int(solved.value)
 
-    # ---- loop-free alternates under drain, metric and restore events ------------------------
+    # ---- loop-free alternates under drain, metric, restore and maintenance events ------------
     def _event_lfa(self, fn, ev, n: int, sources, groups, use_link_metric, nh_bytes, cap, want_counts):
         """The host call ``fn`` over the events ``ev`` (n of them): the tuple whatif_lfa returns."""
         gp, gn = _ignore_arrays(groups, len(groups))
@@ -1433,6 +1437,40 @@ class SpfEngine:
         ev = (vp(d_node_ptr or None), vp(d_nodes or None), vp(d_link_ptr or None), vp(d_links or None),
               vp(d_edge_ptr or None), vp(d_edges or None), vp(d_metrics or None), n_events, n_nodes, n_links, n_edges)
         return self._event_lfa_device(self._lib.openr_spf_whatif_restore_lfa_device, ev, d_sources, n_sources,
+                                      d_group_ptr, d_group_nodes, n_groups, n_group_nodes, d_changed, d_unprotected,
+                                      d_lost_backup, d_ptr, d_group, d_metric, d_nh, d_alt, cap, nh_bytes,
+                                      use_link_metric, stream, device_index, allow_overflow)
+
+    def whatif_maint_lfa(self, node_sets: Optional[Sequence[Sequence[int]]],
+                         link_sets: Optional[Sequence[Sequence[int]]],
+                         edge_sets: Optional[Sequence[Sequence[int]]],
+                         metric_sets: Optional[Sequence[Sequence[int]]], sources: Sequence[int],
+                         groups: Sequence[Sequence[int]], use_link_metric: bool = True,
+                         nh_bytes: Optional[int] = None, cap: Optional[int] = None, want_counts: bool = True):
+        """Loop-free alternates under maintenance events (openr_spf_whatif_maint_lfa): the events
+        of whatif_maint (overloads, link-downs and metric raises in one event), the return tuple
+        of whatif_lfa. Under hop count the raises are ignored: the answer is whatif_drain_lfa's
+        for the nodes and links."""
+        ev, keep, n = self._restore_events(node_sets, link_sets, edge_sets, metric_sets, MaintEvents)
+        out = self._event_lfa(self._lib.openr_spf_whatif_maint_lfa, ev, n, sources, groups, use_link_metric,
+                              nh_bytes, cap, want_counts)
+        del keep
+        return out
+
+    def whatif_maint_lfa_device(self, d_node_ptr: int, d_nodes: int, d_link_ptr: int, d_links: int,
+                                d_edge_ptr: int, d_edges: int, d_metrics: int, n_events: int, n_nodes: int,
+                                n_links: int, n_edges: int, d_sources: int, n_sources: int, d_group_ptr: int,
+                                d_group_nodes: int, n_groups: int, n_group_nodes: int, d_changed: int,
+                                d_unprotected: int = 0, d_lost_backup: int = 0, d_ptr: int = 0, d_group: int = 0,
+                                d_metric: int = 0, d_nh: int = 0, d_alt: int = 0, cap: int = 0,
+                                nh_bytes: int = 0, use_link_metric: bool = True, stream: int = 0,
+                                device_index: int = 0, allow_overflow: bool = False) -> Tuple[int, int]:
+        """Device-pointer form (openr_spf_whatif_maint_lfa_device): (total entries, solved);
+        events as whatif_maint_device, outputs as whatif_lfa_device."""
+        vp = ctypes.c_void_p
+        ev = (vp(d_node_ptr or None), vp(d_nodes or None), vp(d_link_ptr or None), vp(d_links or None),
+              vp(d_edge_ptr or None), vp(d_edges or None), vp(d_metrics or None), n_events, n_nodes, n_links, n_edges)
+        return self._event_lfa_device(self._lib.openr_spf_whatif_maint_lfa_device, ev, d_sources, n_sources,
                                       d_group_ptr, d_group_nodes, n_groups, n_group_nodes, d_changed, d_unprotected,
                                       d_lost_backup, d_ptr, d_group, d_metric, d_nh, d_alt, cap, nh_bytes,
                                       use_link_metric, stream, device_index, allow_overflow)
