@@ -95,11 +95,11 @@ struct Device {
   DevBuf<uint64_t> base_dist, base_tight, wdist;
   DevBuf<uint8_t> base_nh, wnh;
   DevBuf<uint32_t> wsrc, wlink, wunit, wcount, wiota, win_links, win_src, wchanged;
-  DevBuf<uint32_t> wbeg, wend, win_ptr;  // link-set sweep: each listed unit's slice of the set CSR; host form's set_ptr
+  DevBuf<uint32_t> wbeg, wend;  // link-set sweep: each listed unit's slice of the set CSR
   DevBuf<uint32_t> wchanged_t;  // grouped repair: results source-major, transposed into the caller's rows
-  DevBuf<uint32_t> win_nodes, win_lptr;  // drain sweep, host form: the events' nodes and link_ptr (node_ptr: win_ptr)
-  DevBuf<uint32_t> win_edges, win_metrics;  // metric sweep, host form: the events' edges and new metrics (edge_ptr: win_ptr)
-  DevBuf<uint32_t> win_eptr;  // restore sweep, host form: edge_ptr (node_ptr: win_ptr, link_ptr: win_lptr)
+  // host forms, the units' CSRs (upload_whatif_units): node (win_ptr / win_nodes), link (win_lptr /
+  // win_links; single links: win_links alone), edge (win_eptr / win_edges / win_metrics)
+  DevBuf<uint32_t> win_ptr, win_nodes, win_lptr, win_eptr, win_edges, win_metrics;
   DevBuf<uint16_t> base_tin;  // what-if base SPF: tight in-degree rows (rounds plan)
   size_t wiota_n = 0;  // wiota[0, wiota_n) holds 0, 1, 2, ... (kept across calls)
   // KSP2: base rows, chunk rows, per-chunk ignore slots / sources / pointers, status
@@ -1174,6 +1174,19 @@ hipError_t ksp2_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, 
   return hipSuccess;
 }
 
+// The first check of the what-if, event, route and LFA calls.
+int check_ctx(const openr_spf_ctx* ctx) {
+  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
+  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  return OPENR_SPF_OK;
+}
+
+int check_device_index(const openr_spf_ctx* ctx, int device_index) {
+  if (device_index < 0 || device_index >= (int)ctx->devs.size())
+    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+  return OPENR_SPF_OK;
+}
+
 int whatif_plans(openr_spf_ctx* ctx, uint32_t flags, Plan* base_plan, Plan* ign_plan) {
   int rc = make_plan(ctx, flags, false, base_plan);
   if (rc) return rc;
@@ -1264,10 +1277,10 @@ hipError_t whatif_repair_on_device(openr_spf_ctx* ctx, Device& d, const Plan& ba
   return hipSuccess;
 }
 
-hipError_t whatif_drain_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, const WhatifUnits& un,
-                                  const uint32_t* d_sources, uint32_t n_src, uint32_t* d_changed, hipStream_t s,
-                                  uint32_t* solved, bool use_link_metric, const WhatifDelta& dl) {
-  DrainPass p{};
+// The event CSRs of `un` into a pass struct, each where the struct has it: the node and link
+// CSRs (with unit_cost) of a drain, restore or maintenance pass ...
+template <class Pass>
+void fill_node_link_csrs(Pass& p, const WhatifUnits& un, bool use_link_metric) {
   p.n_nodes = un.n_nodes;
   p.n_links = un.n_set_links;
   p.unit_cost = use_link_metric ? 0u : 1u;
@@ -1275,6 +1288,22 @@ hipError_t whatif_drain_on_device(openr_spf_ctx* ctx, Device& d, const Plan& bas
   p.nodes = un.nodes;
   p.link_ptr = un.set_ptr;
   p.links = un.set_links;
+}
+
+// ... and the edge CSR of a metric, restore or maintenance pass.
+template <class Pass>
+void fill_edge_csr(Pass& p, const WhatifUnits& un) {
+  p.n_edges = un.n_edges;
+  p.edge_ptr = un.edge_ptr;
+  p.edges = un.edges;
+  p.metrics = un.metrics;
+}
+
+hipError_t whatif_drain_on_device(openr_spf_ctx* ctx, Device& d, const Plan& base_plan, const WhatifUnits& un,
+                                  const uint32_t* d_sources, uint32_t n_src, uint32_t* d_changed, hipStream_t s,
+                                  uint32_t* solved, bool use_link_metric, const WhatifDelta& dl) {
+  DrainPass p{};
+  fill_node_link_csrs(p, un, use_link_metric);
   return whatif_repair_on_device(ctx, d, base_plan, p, un.n, kDrainCtr, launch_drain_filter, launch_drain_repair,
                                  d_sources, n_src, d_changed, s, solved, dl);
 }
@@ -1286,10 +1315,7 @@ hipError_t whatif_metric_on_device(openr_spf_ctx* ctx, Device& d, const Plan& ba
   *solved = 0;
   if (n_src && un.n && !use_link_metric) return hipErrorInvalidValue;
   MetricPass p{};
-  p.n_edges = un.n_edges;
-  p.edge_ptr = un.edge_ptr;
-  p.edges = un.edges;
-  p.metrics = un.metrics;
+  fill_edge_csr(p, un);
   return whatif_repair_on_device(ctx, d, base_plan, p, un.n, kMetricCtr, launch_metric_filter, launch_metric_repair,
                                  d_sources, n_src, d_changed, s, solved, dl);
 }
@@ -1298,17 +1324,8 @@ hipError_t whatif_restore_on_device(openr_spf_ctx* ctx, Device& d, const Plan& b
                                     const uint32_t* d_sources, uint32_t n_src, uint32_t* d_changed, hipStream_t s,
                                     uint32_t* solved, bool use_link_metric, const WhatifDelta& dl) {
   RestorePass p{};
-  p.n_nodes = un.n_nodes;
-  p.n_links = un.n_set_links;
-  p.n_edges = un.n_edges;
-  p.unit_cost = use_link_metric ? 0u : 1u;
-  p.node_ptr = un.node_ptr;
-  p.nodes = un.nodes;
-  p.link_ptr = un.set_ptr;
-  p.links = un.set_links;
-  p.edge_ptr = un.edge_ptr;
-  p.edges = un.edges;
-  p.metrics = un.metrics;
+  fill_node_link_csrs(p, un, use_link_metric);
+  fill_edge_csr(p, un);
   return whatif_repair_on_device(ctx, d, base_plan, p, un.n, kRestoreCtr, launch_restore_filter,
                                  launch_restore_repair, d_sources, n_src, d_changed, s, solved, dl);
 }
@@ -1317,17 +1334,8 @@ hipError_t whatif_maint_on_device(openr_spf_ctx* ctx, Device& d, const Plan& bas
                                   const uint32_t* d_sources, uint32_t n_src, uint32_t* d_changed, hipStream_t s,
                                   uint32_t* solved, bool use_link_metric, const WhatifDelta& dl) {
   MaintPass p{};
-  p.n_nodes = un.n_nodes;
-  p.n_links = un.n_set_links;
-  p.n_edges = un.n_edges;
-  p.unit_cost = use_link_metric ? 0u : 1u;
-  p.node_ptr = un.node_ptr;
-  p.nodes = un.nodes;
-  p.link_ptr = un.set_ptr;
-  p.links = un.set_links;
-  p.edge_ptr = un.edge_ptr;
-  p.edges = un.edges;
-  p.metrics = un.metrics;
+  fill_node_link_csrs(p, un, use_link_metric);
+  fill_edge_csr(p, un);
   return whatif_repair_on_device(ctx, d, base_plan, p, un.n, kMaintCtr, launch_maint_filter, launch_maint_repair,
                                  d_sources, n_src, d_changed, s, solved, dl);
 }
@@ -1456,216 +1464,120 @@ int whatif_delta_on_device(openr_spf_ctx* ctx, Device& d, const WhatifUnits& un,
   return OPENR_SPF_OK;
 }
 
-// Argument checks of the host what-if forms (hu in host memory: single links or link sets).
+// One CSR of host units: ptr ascends over the n slices, the values are there when a slice is
+// not empty (vals_given: every array the CSR needs), every value is below `bound`. `what`
+// names the values in the messages.
+int check_host_csr(const char* what, const uint32_t* ptr, uint32_t n, const uint32_t* vals, bool vals_given,
+                   uint32_t bound) {
+  for (uint32_t i = 0; i < n; ++i)
+    if (ptr[i + 1] < ptr[i]) return fail(OPENR_SPF_EINVAL, "%s_ptr does not ascend at %u", what, i);
+  if (ptr[n] > ptr[0] && !vals_given) return fail(OPENR_SPF_EINVAL, "null %s values", what);
+  for (uint32_t k = ptr[0]; k < ptr[n]; ++k)
+    if (vals[k] >= bound) return fail(OPENR_SPF_EINVAL, "%s %u out of range (%u of them)", what, vals[k], bound);
+  return OPENR_SPF_OK;
+}
+
+// The rules of an edge CSR beyond check_host_csr: ids strictly ascending inside an event, and
+// every new metric on the side of the current one that the kind allows. A restore event
+// lowers, into [1, current]; a metric or maintenance event raises, into [current, 2^31-1].
+int check_host_edges(const openr_spf_ctx* ctx, const WhatifUnits& hu) {
+  for (uint32_t i = 0; i < hu.n; ++i)
+    for (uint32_t k = hu.edge_ptr[i]; k < hu.edge_ptr[i + 1]; ++k) {
+      const uint32_t e = hu.edges[k], m = hu.metrics[k];
+      if (k > hu.edge_ptr[i] && e <= hu.edges[k - 1])
+        return fail(OPENR_SPF_EINVAL, "event %u: edge ids are not strictly ascending", i);
+      const uint64_t cur = ctx->metric[e];
+      if (hu.restore ? (m > cur || m < 1u) : (m < cur || m > 0x7FFFFFFFu))
+        return fail(OPENR_SPF_EINVAL,
+                    "event %u: metric %u of edge %u is %s (a restore event lowers, openr_spf_whatif_restore; a metric "
+                    "or maintenance event raises)",
+                    i, m, e, hu.restore ? "above the current one or below 1" : "below the current one or above 2^31-1");
+    }
+  return OPENR_SPF_OK;
+}
+
+// Argument checks of the host what-if forms (hu in host memory). EINVAL only.
 int check_whatif_host(const openr_spf_ctx* ctx, const WhatifUnits& hu, const uint32_t* sources, uint32_t n_sources,
                       const uint32_t* changed) {
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
+  int rc = check_ctx(ctx);
+  if (rc) return rc;
   if ((hu.n && !hu.links && !hu.set_ptr && !hu.node_ptr && !hu.edge_ptr) || (n_sources && !sources) ||
       (hu.n && n_sources && !changed))
     return fail(OPENR_SPF_EINVAL, "null links, sources or changed");
   for (uint32_t i = 0; i < n_sources; ++i)
     if (sources[i] >= ctx->V) return fail(OPENR_SPF_EINVAL, "source %u out of range (V=%u)", sources[i], ctx->V);
-  // restore / maintenance events: node CSR, link CSR (nullable), edge CSR (nullable) with lowers / raises only
-  if (hu.restore || hu.maint) {
-    if (hu.n && !hu.node_ptr) return fail(OPENR_SPF_EINVAL, "null node_ptr");
-    for (uint32_t i = 0; i < hu.n; ++i) {
-      if (hu.node_ptr[i + 1] < hu.node_ptr[i]) return fail(OPENR_SPF_EINVAL, "node_ptr does not ascend at event %u", i);
-      if (hu.set_ptr && hu.set_ptr[i + 1] < hu.set_ptr[i])
-        return fail(OPENR_SPF_EINVAL, "link_ptr does not ascend at event %u", i);
-      if (hu.edge_ptr && hu.edge_ptr[i + 1] < hu.edge_ptr[i])
-        return fail(OPENR_SPF_EINVAL, "edge_ptr does not ascend at event %u", i);
-    }
-    if (!hu.n) return OPENR_SPF_OK;
-    if (hu.node_ptr[hu.n] > hu.node_ptr[0] && !hu.nodes) return fail(OPENR_SPF_EINVAL, "null nodes");
-    if (hu.set_ptr && hu.set_ptr[hu.n] > hu.set_ptr[0] && !hu.set_links) return fail(OPENR_SPF_EINVAL, "null links");
-    if (hu.edge_ptr && hu.edge_ptr[hu.n] > hu.edge_ptr[0] && (!hu.edges || !hu.metrics))
-      return fail(OPENR_SPF_EINVAL, "null edges or metrics");
-    for (uint32_t k = hu.node_ptr[0]; k < hu.node_ptr[hu.n]; ++k)
-      if (hu.nodes[k] >= ctx->V) return fail(OPENR_SPF_EINVAL, "node %u out of range (V=%u)", hu.nodes[k], ctx->V);
-    if (hu.set_ptr)
-      for (uint32_t k = hu.set_ptr[0]; k < hu.set_ptr[hu.n]; ++k)
-        if (hu.set_links[k] >= ctx->L)
-          return fail(OPENR_SPF_EINVAL, "link %u out of range (L=%u)", hu.set_links[k], ctx->L);
-    if (hu.edge_ptr)
-      for (uint32_t i = 0; i < hu.n; ++i)
-        for (uint32_t k = hu.edge_ptr[i]; k < hu.edge_ptr[i + 1]; ++k) {
-          const uint32_t e = hu.edges[k];
-          if (e >= ctx->E) return fail(OPENR_SPF_EINVAL, "edge %u out of range (E=%u)", e, ctx->E);
-          if (k > hu.edge_ptr[i] && e <= hu.edges[k - 1])
-            return fail(OPENR_SPF_EINVAL, "event %u: edge ids are not strictly ascending", i);
-          if (hu.maint) {
-            if (hu.metrics[k] < ctx->metric[e] || hu.metrics[k] > 0x7FFFFFFFu)
-              return fail(OPENR_SPF_EINVAL,
-                          "event %u: metric %u of edge %u is below the current one (%llu: a decrease belongs to "
-                          "openr_spf_whatif_restore) or above 2^31-1",
-                          i, hu.metrics[k], e, (unsigned long long)ctx->metric[e]);
-            continue;
-          }
-          if (hu.metrics[k] > ctx->metric[e] || hu.metrics[k] < 1u)
-            return fail(OPENR_SPF_EINVAL,
-                        "event %u: metric %u of edge %u is above the current one (%llu: a raise belongs to "
-                        "openr_spf_whatif_metric) or below 1",
-                        i, hu.metrics[k], e, (unsigned long long)ctx->metric[e]);
-        }
+  if (!hu.n) return OPENR_SPF_OK;
+  if ((hu.restore || hu.maint) && !hu.node_ptr) return fail(OPENR_SPF_EINVAL, "null node_ptr");
+  if (!hu.set_ptr && !hu.node_ptr && !hu.edge_ptr) {  // single links
+    for (uint32_t i = 0; i < hu.n; ++i)
+      if (hu.links[i] >= ctx->L) return fail(OPENR_SPF_EINVAL, "link %u out of range (L=%u)", hu.links[i], ctx->L);
     return OPENR_SPF_OK;
   }
-  if (hu.edge_ptr) {  // metric events: raises only, ids strictly ascending inside an event
-    for (uint32_t i = 0; i < hu.n; ++i)
-      if (hu.edge_ptr[i + 1] < hu.edge_ptr[i]) return fail(OPENR_SPF_EINVAL, "edge_ptr does not ascend at event %u", i);
-    if (hu.edge_ptr[hu.n] > hu.edge_ptr[0] && (!hu.edges || !hu.metrics)) return fail(OPENR_SPF_EINVAL, "null edges or metrics");
-    for (uint32_t i = 0; i < hu.n; ++i)
-      for (uint32_t k = hu.edge_ptr[i]; k < hu.edge_ptr[i + 1]; ++k) {
-        const uint32_t e = hu.edges[k];
-        if (e >= ctx->E) return fail(OPENR_SPF_EINVAL, "edge %u out of range (E=%u)", e, ctx->E);
-        if (k > hu.edge_ptr[i] && e <= hu.edges[k - 1])
-          return fail(OPENR_SPF_EINVAL, "event %u: edge ids are not strictly ascending", i);
-        if (hu.metrics[k] < ctx->metric[e] || hu.metrics[k] > 0x7FFFFFFFu)
-          return fail(OPENR_SPF_EINVAL, "event %u: metric %u of edge %u is below the current one (%llu) or above 2^31-1",
-                      i, hu.metrics[k], e, (unsigned long long)ctx->metric[e]);
-      }
-    return OPENR_SPF_OK;
+  // sets: the link CSR; drain events: node and link CSR; metric events: the edge CSR; restore and
+  // maintenance events: all three (the link and the edge CSR nullable wherever a node CSR leads)
+  if (hu.node_ptr) rc = check_host_csr("node", hu.node_ptr, hu.n, hu.nodes, hu.nodes != nullptr, ctx->V);
+  if (!rc && hu.set_ptr) rc = check_host_csr("link", hu.set_ptr, hu.n, hu.set_links, hu.set_links != nullptr, ctx->L);
+  if (!rc && hu.edge_ptr) {
+    rc = check_host_csr("edge", hu.edge_ptr, hu.n, hu.edges, hu.edges && hu.metrics, ctx->E);
+    if (!rc) rc = check_host_edges(ctx, hu);
   }
-  if (hu.node_ptr) {  // drain events: the node CSR here, the link CSR (nullable) below
-    for (uint32_t i = 0; i < hu.n; ++i)
-      if (hu.node_ptr[i + 1] < hu.node_ptr[i]) return fail(OPENR_SPF_EINVAL, "node_ptr does not ascend at event %u", i);
-    if (hu.node_ptr[hu.n] > hu.node_ptr[0] && !hu.nodes) return fail(OPENR_SPF_EINVAL, "null nodes");
-    for (uint32_t k = hu.node_ptr[0]; k < hu.node_ptr[hu.n]; ++k)
-      if (hu.nodes[k] >= ctx->V) return fail(OPENR_SPF_EINVAL, "node %u out of range (V=%u)", hu.nodes[k], ctx->V);
-    if (!hu.set_ptr) return OPENR_SPF_OK;
-  }
-  if (!hu.set_ptr) {
-    for (uint32_t i = 0; i < hu.n; ++i)
-      if (hu.links[i] >= ctx->L)
-        return fail(OPENR_SPF_EINVAL, "link %u out of range (L=%u)", hu.links[i], ctx->L);
-    return OPENR_SPF_OK;
-  }
-  for (uint32_t i = 0; i < hu.n; ++i)
-    if (hu.set_ptr[i + 1] < hu.set_ptr[i]) return fail(OPENR_SPF_EINVAL, "set_ptr does not ascend at set %u", i);
-  if (hu.set_ptr[hu.n] > hu.set_ptr[0] && !hu.set_links) return fail(OPENR_SPF_EINVAL, "null set_links");
-  for (uint32_t k = hu.set_ptr[0]; k < hu.set_ptr[hu.n]; ++k)
-    if (hu.set_links[k] >= ctx->L)
-      return fail(OPENR_SPF_EINVAL, "link %u out of range (L=%u)", hu.set_links[k], ctx->L);
-  return OPENR_SPF_OK;
+  return rc;
 }
 
-// Units [b, b + m) of hu into the device's input buffers on its stream (*un: the device
-// view). A block of sets takes its slice of set_links, and its set_ptr rebased to that slice.
+// Units [b, b + m) of hu into the device's input buffers on its stream (*un: the device view).
+// Single links are copied as they are. A CSR goes through `block`: its ptr rebased to the
+// block's slice, the slice of its values behind it. Every CSR has buffers of its own (node:
+// win_ptr / win_nodes, link: win_lptr / win_links, edge: win_eptr / win_edges / win_metrics).
 int upload_whatif_units(Device& d, const WhatifUnits& hu, uint32_t b, uint32_t m, std::vector<uint32_t>* rebased,
                         WhatifUnits* un) {
   *un = WhatifUnits{};
   un->n = m;
-  // restore / maintenance events: win_ptr / win_nodes, win_lptr / win_links, win_eptr / win_edges / win_metrics
-  if (hu.restore || hu.maint) {
-    // one CSR's block: ptr rebased to the block's slice, the slice of vals (and vals2) behind it
-    auto block = [&](const uint32_t* ptr, const uint32_t* vals, const uint32_t* vals2, DevBuf<uint32_t>& dptr,
-                     DevBuf<uint32_t>& dvals, DevBuf<uint32_t>* dvals2, uint32_t* count) -> int {
-      const uint32_t b0 = ptr[b], e0 = ptr[b + m];
-      rebased->resize(m + 1);
-      for (uint32_t i = 0; i <= m; ++i) (*rebased)[i] = ptr[b + i] - b0;
-      HIP_TRY(dptr.reserve(m + 1));
-      HIP_TRY(dvals.reserve(std::max<uint32_t>(e0 - b0, 1u)));
-      if (dvals2) HIP_TRY(dvals2->reserve(std::max<uint32_t>(e0 - b0, 1u)));
-      HIP_TRY(hipMemcpyAsync(dptr.p, rebased->data(), (m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
-      if (e0 > b0) {
-        HIP_TRY(hipMemcpyAsync(dvals.p, vals + b0, (e0 - b0) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
-        if (dvals2)
-          HIP_TRY(hipMemcpyAsync(dvals2->p, vals2 + b0, (e0 - b0) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
-      }
-      HIP_TRY(hipStreamSynchronize(d.stream));  // `rebased` is reused for the next CSR and the next device's block
-      *count = e0 - b0;
-      return OPENR_SPF_OK;
-    };
-    un->restore = hu.restore;
-    un->maint = hu.maint;
-    int rc = block(hu.node_ptr, hu.nodes, nullptr, d.win_ptr, d.win_nodes, nullptr, &un->n_nodes);
-    if (rc) return rc;
-    un->node_ptr = d.win_ptr.p;
-    un->nodes = d.win_nodes.p;
-    if (hu.set_ptr) {
-      if ((rc = block(hu.set_ptr, hu.set_links, nullptr, d.win_lptr, d.win_links, nullptr, &un->n_set_links))) return rc;
-      un->set_ptr = d.win_lptr.p;
-      un->set_links = d.win_links.p;
-    }
-    if (hu.edge_ptr) {
-      if ((rc = block(hu.edge_ptr, hu.edges, hu.metrics, d.win_eptr, d.win_edges, &d.win_metrics, &un->n_edges))) return rc;
-      un->edge_ptr = d.win_eptr.p;
-      un->edges = d.win_edges.p;
-      un->metrics = d.win_metrics.p;
-    }
-    return OPENR_SPF_OK;
-  }
-  if (hu.edge_ptr) {  // metric events: edge CSR in win_ptr / win_edges / win_metrics
-    const uint32_t eb = hu.edge_ptr[b], ee = hu.edge_ptr[b + m];
-    rebased->resize(m + 1);
-    for (uint32_t i = 0; i <= m; ++i) (*rebased)[i] = hu.edge_ptr[b + i] - eb;
-    HIP_TRY(d.win_ptr.reserve(m + 1));
-    HIP_TRY(d.win_edges.reserve(std::max<uint32_t>(ee - eb, 1u)));
-    HIP_TRY(d.win_metrics.reserve(std::max<uint32_t>(ee - eb, 1u)));
-    HIP_TRY(hipMemcpyAsync(d.win_ptr.p, rebased->data(), (m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
-    if (ee > eb) {
-      HIP_TRY(hipMemcpyAsync(d.win_edges.p, hu.edges + eb, (ee - eb) * sizeof(uint32_t), hipMemcpyHostToDevice,
-                             d.stream));
-      HIP_TRY(hipMemcpyAsync(d.win_metrics.p, hu.metrics + eb, (ee - eb) * sizeof(uint32_t), hipMemcpyHostToDevice,
-                             d.stream));
-    }
-    HIP_TRY(hipStreamSynchronize(d.stream));  // `rebased` is reused for the next device's block
-    un->edge_ptr = d.win_ptr.p;
-    un->edges = d.win_edges.p;
-    un->metrics = d.win_metrics.p;
-    un->n_edges = ee - eb;
-    return OPENR_SPF_OK;
-  }
-  if (hu.node_ptr) {  // drain events: node CSR in win_ptr / win_nodes, link CSR in win_lptr / win_links
-    const uint32_t nb0 = hu.node_ptr[b], ne0 = hu.node_ptr[b + m];
-    rebased->resize(m + 1);
-    for (uint32_t i = 0; i <= m; ++i) (*rebased)[i] = hu.node_ptr[b + i] - nb0;
-    HIP_TRY(d.win_ptr.reserve(m + 1));
-    HIP_TRY(d.win_nodes.reserve(std::max<uint32_t>(ne0 - nb0, 1u)));
-    HIP_TRY(hipMemcpyAsync(d.win_ptr.p, rebased->data(), (m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
-    if (ne0 > nb0)
-      HIP_TRY(hipMemcpyAsync(d.win_nodes.p, hu.nodes + nb0, (ne0 - nb0) * sizeof(uint32_t), hipMemcpyHostToDevice,
-                             d.stream));
-    HIP_TRY(hipStreamSynchronize(d.stream));  // `rebased` is reused below and for the next device's block
-    un->node_ptr = d.win_ptr.p;
-    un->nodes = d.win_nodes.p;
-    un->n_nodes = ne0 - nb0;
-    if (!hu.set_ptr) return OPENR_SPF_OK;
-    const uint32_t lb = hu.set_ptr[b], le = hu.set_ptr[b + m];
-    for (uint32_t i = 0; i <= m; ++i) (*rebased)[i] = hu.set_ptr[b + i] - lb;
-    HIP_TRY(d.win_lptr.reserve(m + 1));
-    HIP_TRY(d.win_links.reserve(std::max<uint32_t>(le - lb, 1u)));
-    HIP_TRY(hipMemcpyAsync(d.win_lptr.p, rebased->data(), (m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
-    if (le > lb)
-      HIP_TRY(hipMemcpyAsync(d.win_links.p, hu.set_links + lb, (le - lb) * sizeof(uint32_t), hipMemcpyHostToDevice,
-                             d.stream));
-    HIP_TRY(hipStreamSynchronize(d.stream));
-    un->set_ptr = d.win_lptr.p;
-    un->set_links = d.win_links.p;
-    un->n_set_links = le - lb;
-    return OPENR_SPF_OK;
-  }
-  if (!hu.set_ptr) {
+  un->restore = hu.restore;
+  un->maint = hu.maint;
+  if (!hu.set_ptr && !hu.node_ptr && !hu.edge_ptr) {  // no rebase, so nothing to wait for
     HIP_TRY(d.win_links.reserve(m));
     HIP_TRY(hipMemcpyAsync(d.win_links.p, hu.links + b, m * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
     un->links = d.win_links.p;
     return OPENR_SPF_OK;
   }
-  const uint32_t lb = hu.set_ptr[b], le = hu.set_ptr[b + m];
-  rebased->resize(m + 1);
-  for (uint32_t i = 0; i <= m; ++i) (*rebased)[i] = hu.set_ptr[b + i] - lb;
-  HIP_TRY(d.win_ptr.reserve(m + 1));
-  HIP_TRY(d.win_links.reserve(std::max<uint32_t>(le - lb, 1u)));
-  HIP_TRY(hipMemcpyAsync(d.win_ptr.p, rebased->data(), (m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
-  if (le > lb)
-    HIP_TRY(hipMemcpyAsync(d.win_links.p, hu.set_links + lb, (le - lb) * sizeof(uint32_t), hipMemcpyHostToDevice,
-                           d.stream));
-  HIP_TRY(hipStreamSynchronize(d.stream));  // `rebased` is reused for the next device's block
-  un->set_ptr = d.win_ptr.p;
-  un->set_links = d.win_links.p;
-  un->n_set_links = le - lb;
+  auto block = [&](const uint32_t* ptr, const uint32_t* vals, const uint32_t* vals2, DevBuf<uint32_t>& dptr,
+                   DevBuf<uint32_t>& dvals, DevBuf<uint32_t>* dvals2, uint32_t* count) -> int {
+    const uint32_t b0 = ptr[b], e0 = ptr[b + m];
+    rebased->resize(m + 1);
+    for (uint32_t i = 0; i <= m; ++i) (*rebased)[i] = ptr[b + i] - b0;
+    HIP_TRY(dptr.reserve(m + 1));
+    HIP_TRY(dvals.reserve(std::max<uint32_t>(e0 - b0, 1u)));
+    if (dvals2) HIP_TRY(dvals2->reserve(std::max<uint32_t>(e0 - b0, 1u)));
+    HIP_TRY(hipMemcpyAsync(dptr.p, rebased->data(), (m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    if (e0 > b0) {
+      HIP_TRY(hipMemcpyAsync(dvals.p, vals + b0, (e0 - b0) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+      if (dvals2)
+        HIP_TRY(hipMemcpyAsync(dvals2->p, vals2 + b0, (e0 - b0) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    }
+    HIP_TRY(hipStreamSynchronize(d.stream));  // `rebased` is reused for the next CSR and the next device's block
+    *count = e0 - b0;
+    return OPENR_SPF_OK;
+  };
+  int rc;
+  if (hu.node_ptr) {
+    if ((rc = block(hu.node_ptr, hu.nodes, nullptr, d.win_ptr, d.win_nodes, nullptr, &un->n_nodes))) return rc;
+    un->node_ptr = d.win_ptr.p;
+    un->nodes = d.win_nodes.p;
+  }
+  if (hu.set_ptr) {
+    if ((rc = block(hu.set_ptr, hu.set_links, nullptr, d.win_lptr, d.win_links, nullptr, &un->n_set_links))) return rc;
+    un->set_ptr = d.win_lptr.p;
+    un->set_links = d.win_links.p;
+  }
+  if (hu.edge_ptr) {
+    if ((rc = block(hu.edge_ptr, hu.edges, hu.metrics, d.win_eptr, d.win_edges, &d.win_metrics, &un->n_edges))) return rc;
+    un->edge_ptr = d.win_eptr.p;
+    un->edges = d.win_edges.p;
+    un->metrics = d.win_metrics.p;
+  }
   return OPENR_SPF_OK;
 }
+
 
 // openr_spf_whatif / openr_spf_whatif_sets: units split in contiguous blocks across the devices
 int whatif_host(openr_spf_ctx* ctx, const WhatifUnits& hu, const uint32_t* sources, uint32_t n_sources,
@@ -1806,16 +1718,13 @@ int whatif_delta_host(openr_spf_ctx* ctx, const WhatifUnits& hu, const uint32_t*
 // openr_spf_whatif_device / openr_spf_whatif_sets_device (un in device memory)
 int whatif_device_form(openr_spf_ctx* ctx, int device_index, const WhatifUnits& un, const uint32_t* d_sources,
                        uint32_t n_sources, uint32_t flags, uint32_t* d_changed, void* stream, uint64_t* out_solved) {
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (device_index < 0 || device_index >= (int)ctx->devs.size())
-    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+  int rc = check_ctx(ctx);
+  if (rc || (rc = check_device_index(ctx, device_index))) return rc;
   if ((un.n && !un.links && !un.set_ptr && !un.node_ptr && !un.edge_ptr) || (n_sources && !d_sources) ||
       (un.n && n_sources && !d_changed))
     return fail(OPENR_SPF_EINVAL, "null links, sources or changed");
   Plan bp, ip;
-  int rc = whatif_plans(ctx, flags, &bp, &ip);
-  if (rc) return rc;
+  if ((rc = whatif_plans(ctx, flags, &bp, &ip))) return rc;
   Device& d = ctx->devs[device_index];
   HIP_TRY(hipSetDevice(d.ordinal));
   hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d.stream;
@@ -1834,10 +1743,8 @@ int whatif_delta_device_form(openr_spf_ctx* ctx, int device_index, const WhatifU
                              uint32_t n_sources, uint32_t flags, uint32_t* d_changed, uint64_t* d_ptr,
                              uint32_t* d_node, uint64_t* d_dist, uint8_t* d_nh, uint64_t cap, uint32_t nh_bytes,
                              void* stream, uint64_t* out_total, uint64_t* out_solved) {
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (device_index < 0 || device_index >= (int)ctx->devs.size())
-    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+  int rc = check_ctx(ctx);
+  if (rc || (rc = check_device_index(ctx, device_index))) return rc;
   if ((un.n && !un.links && !un.set_ptr && !un.node_ptr && !un.edge_ptr) || (n_sources && !d_sources) ||
       (un.n && n_sources && !d_changed) || !d_ptr)
     return fail(OPENR_SPF_EINVAL, "null links, sources, changed or ptr");
@@ -1846,7 +1753,7 @@ int whatif_delta_device_form(openr_spf_ctx* ctx, int device_index, const WhatifU
   HIP_TRY(hipSetDevice(d.ordinal));
   hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d.stream;
   uint64_t total = 0, solved = 0;
-  const int rc = whatif_delta_on_device(ctx, d, un, d_sources, n_sources, flags, d_changed, d_ptr, d_node,
+  rc = whatif_delta_on_device(ctx, d, un, d_sources, n_sources, flags, d_changed, d_ptr, d_node,
                                         reinterpret_cast<unsigned long long*>(d_dist), d_nh, cap, nh_bytes, s, &total,
                                         &solved);
   if (out_total) *out_total = total;
@@ -1886,18 +1793,6 @@ WhatifUnits drain_units(const uint32_t* node_ptr, const uint32_t* nodes, const u
   return un;
 }
 
-int check_drain_events(const openr_spf_ctx* ctx, const openr_spf_drain_events_t* ev) {
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (!ev) return fail(OPENR_SPF_EINVAL, "null events");
-  if (ev->n_events && !ev->node_ptr) return fail(OPENR_SPF_EINVAL, "null node_ptr");
-  return OPENR_SPF_OK;
-}
-
-WhatifUnits host_drain(const openr_spf_drain_events_t* ev) {
-  return drain_units(ev->node_ptr, ev->nodes, ev->link_ptr, ev->links, ev->n_events, 0u, 0u);
-}
-
 // Metric events as what-if units (host or device memory; n_edges: the device form's slice length).
 WhatifUnits metric_units(const uint32_t* edge_ptr, const uint32_t* edges, const uint32_t* metrics, uint32_t n_events,
                          uint32_t n_edges) {
@@ -1908,18 +1803,6 @@ WhatifUnits metric_units(const uint32_t* edge_ptr, const uint32_t* edges, const 
   un.n_edges = n_edges;
   un.n = n_events;
   return un;
-}
-
-int check_metric_events(const openr_spf_ctx* ctx, const openr_spf_metric_events_t* ev) {
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (!ev) return fail(OPENR_SPF_EINVAL, "null events");
-  if (ev->n_events && !ev->edge_ptr) return fail(OPENR_SPF_EINVAL, "null edge_ptr");
-  return OPENR_SPF_OK;
-}
-
-WhatifUnits host_metric(const openr_spf_metric_events_t* ev) {
-  return metric_units(ev->edge_ptr, ev->edges, ev->metrics, ev->n_events, 0u);
 }
 
 // Restore events as what-if units (host or device memory; the counts: the device form's slice lengths).
@@ -1946,6 +1829,90 @@ WhatifUnits maint_units(const uint32_t* node_ptr, const uint32_t* nodes, const u
   un.restore = false;
   un.maint = true;
   return un;
+}
+
+// The events struct of a host form as what-if units, one overload per family.
+WhatifUnits host_units(const openr_spf_drain_events_t* ev) {
+  return drain_units(ev->node_ptr, ev->nodes, ev->link_ptr, ev->links, ev->n_events, 0u, 0u);
+}
+WhatifUnits host_units(const openr_spf_metric_events_t* ev) {
+  return metric_units(ev->edge_ptr, ev->edges, ev->metrics, ev->n_events, 0u);
+}
+WhatifUnits host_units(const openr_spf_restore_events_t* ev) {
+  return restore_units(ev->node_ptr, ev->nodes, ev->link_ptr, ev->links, ev->edge_ptr, ev->edges, ev->metrics,
+                       ev->n_events, 0u, 0u, 0u);
+}
+WhatifUnits host_units(const openr_spf_maint_events_t* ev) {
+  return maint_units(ev->node_ptr, ev->nodes, ev->link_ptr, ev->links, ev->edge_ptr, ev->edges, ev->metrics,
+                     ev->n_events, 0u, 0u, 0u);
+}
+
+// The plan and capacity check of an event family (ElfaFamily names the four).
+int check_family(const openr_spf_ctx* ctx, int fam, uint32_t flags, uint64_t n_events, uint64_t n_sources) {
+  switch (fam) {
+    case kElfaDrain: return check_drain(ctx, flags, n_events, n_sources);
+    case kElfaMetric: return check_metric(ctx, flags, n_events, n_sources);
+    case kElfaRestore: return check_restore(ctx, flags, n_events, n_sources);
+    default: return check_maint(ctx, flags, n_events, n_sources);
+  }
+}
+
+// The hop-count form of a metric sweep: metrics do not enter runSpf(src, false), so every
+// count is 0, ptr is all zero and no kernel is launched (metric_hops_host / _device). The LFA
+// forms do not take this exit: their pass still counts the unprotected groups.
+bool metric_hops(int fam, uint32_t flags) { return fam == kElfaMetric && !(flags & OPENR_SPF_USE_LINK_METRIC); }
+
+// Events built from the pointers and counts of a device form: an event pointer is null where
+// its count is not. The CSR that makes the units events is the node CSR, or a metric event's
+// edge CSR; the link CSR, and the edge CSR next to a node CSR, may be null.
+bool event_pointer_missing(const WhatifUnits& un) {
+  if (!un.n) return false;
+  if (!un.node_ptr && (un.restore || un.maint || !un.edge_ptr)) return true;
+  return (un.n_nodes && !un.nodes) || (un.set_ptr && un.n_set_links && !un.set_links) ||
+         (un.edge_ptr && un.n_edges && (!un.edges || !un.metrics));
+}
+
+// Under link metric, the links of a restore event whose restored edges would leave the fast
+// plans: an edge comes up with its current metric, or with the event's own entry for it.
+int check_restored_links(const openr_spf_ctx* ctx, const WhatifUnits& hu, uint32_t flags) {
+  if (!(flags & OPENR_SPF_USE_LINK_METRIC) || !hu.set_ptr) return OPENR_SPF_OK;
+  for (uint32_t i = 0; i < hu.n; ++i)
+    for (uint32_t k = hu.set_ptr[i]; k < hu.set_ptr[i + 1]; ++k) {
+      const uint2 de = ctx->ledge[hu.set_links[k]];
+      if (de.x == UINT32_MAX) continue;  // unused id
+      for (const uint32_t e : {de.x, de.y}) {
+        uint64_t m = ctx->metric[e];
+        if (hu.edge_ptr) {  // the event's own entry for e, if any
+          const uint32_t* b = hu.edges + hu.edge_ptr[i];
+          const uint32_t* en = hu.edges + hu.edge_ptr[i + 1];
+          const uint32_t* it = std::lower_bound(b, en, e);
+          if (it != en && *it == e) m = hu.metrics[it - hu.edges];
+        }
+        if (m == 0 || m > 0x7FFFFFFFull)
+          return fail(OPENR_SPF_ENOTSUP,
+                      "event %u: link %u would come up with metric %llu on edge %u, outside [1, 2^31-1] (the base "
+                      "plans after the event would need the exact-order kernel)",
+                      i, hu.set_links[k], (unsigned long long)m, e);
+      }
+    }
+  return OPENR_SPF_OK;
+}
+
+// The checks of an event call's host forms, in the order every family keeps: EINVAL first (the
+// struct here, then sources, changed and the values in check_whatif_host), then the family's
+// ENOTSUP / E2BIG, then a restore's links (ENOTSUP). *hu: the events as units.
+template <class Events>
+int check_events_host(const openr_spf_ctx* ctx, int fam, const Events* ev, const uint32_t* sources,
+                      uint32_t n_sources, uint32_t flags, const uint32_t* changed, WhatifUnits* hu) {
+  int rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!ev) return fail(OPENR_SPF_EINVAL, "null events");
+  *hu = host_units(ev);
+  if (hu->n && !(fam == kElfaMetric ? hu->edge_ptr : hu->node_ptr))
+    return fail(OPENR_SPF_EINVAL, "null %s", fam == kElfaMetric ? "edge_ptr" : "node_ptr");
+  if ((rc = check_whatif_host(ctx, *hu, sources, n_sources, changed)) != OPENR_SPF_OK) return rc;
+  if ((rc = check_family(ctx, fam, flags, hu->n, n_sources)) != OPENR_SPF_OK) return rc;
+  return fam == kElfaRestore ? check_restored_links(ctx, *hu, flags) : OPENR_SPF_OK;
 }
 
 // ---- route-level calls (spf_routes.hip) ---------------------------------------------------
@@ -2966,6 +2933,191 @@ int whatif_lfa_host(openr_spf_ctx* ctx, const WhatifUnits& hu, const uint32_t* s
   return OPENR_SPF_OK;
 }
 
+// ---- the call forms of the event families: one body each ------------------------------------
+// A public function builds its units (device forms) or names its family and calls one of these.
+
+// metric_hops in host memory (delta: the caller's openr_spf_whatif_delta_t or _routes_t, nullable).
+template <class Delta>
+int metric_hops_host(uint32_t n_events, uint32_t n_sources, uint32_t* changed, Delta* delta, uint64_t* out_solved) {
+  if (delta && !delta->ptr) return fail(OPENR_SPF_EINVAL, "null delta->ptr");
+  const size_t units = (size_t)n_events * n_sources;
+  if (units) std::memset(changed, 0, units * sizeof(uint32_t));
+  if (delta) std::memset(delta->ptr, 0, (units + 1) * sizeof(uint64_t));
+  if (out_solved) *out_solved = 0;
+  return OPENR_SPF_OK;
+}
+
+// metric_hops in device memory.
+int metric_hops_device(openr_spf_ctx* ctx, int device_index, uint32_t n_events, uint32_t n_sources,
+                       uint32_t* d_changed, uint64_t* d_ptr, void* stream, uint64_t* out_total,
+                       uint64_t* out_solved) {
+  Device& d = ctx->devs[device_index];
+  HIP_TRY(hipSetDevice(d.ordinal));
+  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d.stream;
+  const size_t units = (size_t)n_events * n_sources;
+  if (units) HIP_TRY(hipMemsetAsync(d_changed, 0, units * sizeof(uint32_t), s));
+  HIP_TRY(hipMemsetAsync(d_ptr, 0, (units + 1) * sizeof(uint64_t), s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (out_total) *out_total = 0;
+  if (out_solved) *out_solved = 0;
+  return OPENR_SPF_OK;
+}
+
+// openr_spf_whatif_<family>
+template <class Events>
+int event_host(openr_spf_ctx* ctx, int fam, const Events* ev, const uint32_t* sources, uint32_t n_sources,
+               uint32_t flags, uint32_t* changed, openr_spf_whatif_delta_t* delta, uint64_t* out_solved) {
+  clear_launch_trace();
+  WhatifUnits hu;
+  const int rc = check_events_host(ctx, fam, ev, sources, n_sources, flags, changed, &hu);
+  if (rc) return rc;
+  if (metric_hops(fam, flags)) return metric_hops_host(hu.n, n_sources, changed, delta, out_solved);
+  if (!delta) return whatif_host(ctx, hu, sources, n_sources, flags, changed, out_solved);
+  return whatif_delta_host(ctx, hu, sources, n_sources, flags, changed, delta, out_solved);
+}
+
+// openr_spf_whatif_<family>_routes
+template <class Events>
+int event_routes_host(openr_spf_ctx* ctx, int fam, const Events* ev, const uint32_t* sources, uint32_t n_sources,
+                      uint32_t flags, const openr_spf_groups_t* groups, uint32_t* changed_routes,
+                      openr_spf_whatif_routes_t* delta, uint64_t* out_solved) {
+  clear_launch_trace();
+  WhatifUnits hu;
+  int rc = check_events_host(ctx, fam, ev, sources, n_sources, flags, changed_routes, &hu);
+  if (rc) return rc;
+  if (metric_hops(fam, flags)) {
+    if ((rc = check_groups_host(ctx, groups)) != OPENR_SPF_OK) return rc;
+    return metric_hops_host(hu.n, n_sources, changed_routes, delta, out_solved);
+  }
+  return whatif_routes_host(ctx, hu, sources, n_sources, flags, groups, changed_routes, delta, out_solved);
+}
+
+// The family's capacity check for a call whose only E2BIG is "sum(changed) > cap": a graph
+// whose repair unit does not fit LDS is not supported by these calls.
+int event_lfa_check(int rc) { return rc == OPENR_SPF_E2BIG ? OPENR_SPF_ENOTSUP : rc; }
+
+// openr_spf_whatif_<family>_lfa (whatif_lfa_host clears the launch trace)
+template <class Events>
+int event_lfa_host(openr_spf_ctx* ctx, int fam, const Events* ev, const uint32_t* sources, uint32_t n_sources,
+                   uint32_t flags, const openr_spf_groups_t* groups, uint32_t* changed, uint32_t* unprotected,
+                   uint32_t* lost_backup, openr_spf_whatif_lfa_t* delta, uint64_t* out_solved) {
+  if (out_solved) *out_solved = 0;
+  WhatifUnits hu;
+  const int rc = event_lfa_check(check_events_host(ctx, fam, ev, sources, n_sources, flags, changed, &hu));
+  if (rc) return rc;
+  return whatif_lfa_host(ctx, hu, sources, n_sources, flags, groups, changed, unprotected, lost_backup, delta,
+                         out_solved, fam);
+}
+
+// openr_spf_whatif_<family>_device (un: the events in device memory). The family's check comes
+// before device_index is looked at.
+int event_device(openr_spf_ctx* ctx, int device_index, const WhatifUnits& un, int fam, const uint32_t* d_sources,
+                 uint32_t n_sources, uint32_t flags, uint32_t* d_changed, uint64_t* d_ptr, uint32_t* d_node,
+                 uint64_t* d_dist, uint8_t* d_nh, uint64_t cap, uint32_t nh_bytes, void* stream, uint64_t* out_total,
+                 uint64_t* out_solved) {
+  clear_launch_trace();
+  int rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (event_pointer_missing(un)) return fail(OPENR_SPF_EINVAL, "an event pointer is null where its count is not");
+  if ((rc = check_family(ctx, fam, flags, un.n, n_sources)) != OPENR_SPF_OK) return rc;
+  if (metric_hops(fam, flags)) {
+    if ((rc = check_device_index(ctx, device_index)) != OPENR_SPF_OK) return rc;
+    if ((n_sources && !d_sources) || (un.n && n_sources && !d_changed) || !d_ptr)
+      return fail(OPENR_SPF_EINVAL, "null sources, changed or ptr");
+    return metric_hops_device(ctx, device_index, un.n, n_sources, d_changed, d_ptr, stream, out_total, out_solved);
+  }
+  return whatif_delta_device_form(ctx, device_index, un, d_sources, n_sources, flags, d_changed, d_ptr, d_node, d_dist,
+                                  d_nh, cap, nh_bytes, stream, out_total, out_solved);
+}
+
+// openr_spf_whatif_routes_device (fam < 0: un holds link sets) and openr_spf_whatif_<family>_routes_device
+// (un: the events in device memory). device_index and the null pointers come before the
+// family's check here.
+int whatif_routes_device_form(openr_spf_ctx* ctx, int device_index, const WhatifUnits& un, int fam,
+                              const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
+                              const uint32_t* d_group_ptr, const uint32_t* d_group_nodes, uint32_t n_groups,
+                              uint32_t n_group_nodes, uint32_t* d_changed_routes, uint64_t* d_ptr, uint32_t* d_group,
+                              uint64_t* d_metric, uint8_t* d_nh, uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes,
+                              void* stream, uint64_t* out_total, uint64_t* out_solved) {
+  clear_launch_trace();
+  int rc = check_ctx(ctx);
+  if (rc || (rc = check_device_index(ctx, device_index))) return rc;
+  if ((fam < 0 ? un.n && !un.set_ptr : event_pointer_missing(un)) || (n_sources && !d_sources) ||
+      (un.n && n_sources && !d_changed_routes) || !d_ptr)
+    return fail(OPENR_SPF_EINVAL, "null units, sources, changed_routes or ptr");
+  if ((n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes))
+    return fail(OPENR_SPF_EINVAL, "null group_ptr or group_nodes");
+  if (cap && (!d_group || !d_metric || !d_nh)) return fail(OPENR_SPF_EINVAL, "null route buffer");
+  rc = fam < 0 ? check_routes_metric(ctx, flags) : check_family(ctx, fam, flags, un.n, n_sources);
+  if (rc) return rc;
+  if (metric_hops(fam, flags))
+    return metric_hops_device(ctx, device_index, un.n, n_sources, d_changed_routes, d_ptr, stream, out_total,
+                              out_solved);
+  Device& d = ctx->devs[device_index];
+  HIP_TRY(hipSetDevice(d.ordinal));
+  DevGroups gr;
+  gr.ptr = d_group_ptr;
+  gr.nodes = d_group_nodes;
+  gr.n = n_groups;
+  gr.m = n_group_nodes;
+  uint64_t total = 0, solved = 0;
+  rc = whatif_routes_on_device(ctx, d, un, d_sources, n_sources, flags, gr, d_changed_routes, d_ptr, d_group, d_metric,
+                               d_nh, d_n_best, cap, nh_bytes,
+                               stream ? reinterpret_cast<hipStream_t>(stream) : d.stream, &total, &solved);
+  if (out_total) *out_total = total;
+  if (out_solved) *out_solved = solved;
+  return rc;
+}
+
+// openr_spf_whatif_<family>_lfa_device (un: events of ElfaFamily fam in device memory). The
+// family's check comes before device_index is looked at.
+int event_lfa_device(openr_spf_ctx* ctx, int device_index, const WhatifUnits& un, int fam,
+                     const uint32_t* d_sources, uint32_t n_sources, uint32_t flags, const uint32_t* d_group_ptr,
+                     const uint32_t* d_group_nodes, uint32_t n_groups, uint32_t n_group_nodes, uint32_t* d_changed,
+                     uint32_t* d_unprotected, uint32_t* d_lost_backup, uint64_t* d_ptr, uint32_t* d_group,
+                     uint64_t* d_metric, uint8_t* d_nh, uint8_t* d_alt, uint64_t cap, uint32_t nh_bytes, void* stream,
+                     uint64_t* out_total, uint64_t* out_solved) {
+  clear_launch_trace();
+  if (out_total) *out_total = 0;
+  if (out_solved) *out_solved = 0;
+  int rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (event_pointer_missing(un)) return fail(OPENR_SPF_EINVAL, "an event pointer is null where its count is not");
+  if ((rc = event_lfa_check(check_family(ctx, fam, flags, un.n, n_sources))) != OPENR_SPF_OK) return rc;
+  if ((rc = check_device_index(ctx, device_index)) != OPENR_SPF_OK) return rc;
+  if ((n_sources && !d_sources) || (un.n && n_sources && !d_changed))
+    return fail(OPENR_SPF_EINVAL, "null sources or changed");
+  if ((n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes))
+    return fail(OPENR_SPF_EINVAL, "null group_ptr or group_nodes");
+  if (cap && (!d_ptr || !d_group || !d_metric || !d_nh || !d_alt)) return fail(OPENR_SPF_EINVAL, "null entry buffer");
+  if ((rc = check_routes_metric(ctx, flags)) != OPENR_SPF_OK) return rc;
+  Device& d = ctx->devs[device_index];
+  HIP_TRY(hipSetDevice(d.ordinal));
+  DevGroups gr;
+  gr.ptr = d_group_ptr;
+  gr.nodes = d_group_nodes;
+  gr.n = n_groups;
+  gr.m = n_group_nodes;
+  WlfaOut out;
+  out.changed = d_changed;
+  out.unprot = d_unprotected;
+  out.lost = d_lost_backup;
+  out.ptr = d_ptr;
+  out.group = d_group;
+  out.metric = d_metric;
+  out.nh = d_nh;
+  out.alt = d_alt;
+  out.cap = cap;
+  out.nhb = nh_bytes;
+  uint64_t total = 0, solved = 0;
+  rc = whatif_lfa_on_device(ctx, d, un, d_sources, n_sources, flags, gr, out,
+                            stream ? reinterpret_cast<hipStream_t>(stream) : d.stream, &total, &solved, fam);
+  if (out_total) *out_total = total;
+  if (out_solved) *out_solved = solved;
+  return rc;
+}
+
+
 }  // namespace
 
 extern "C" {
@@ -3910,17 +4062,11 @@ int openr_spf_whatif_sets_delta(openr_spf_ctx* ctx, const uint32_t* set_ptr, con
                            out_solved);
 }
 
+// ---- event sweeps: drain, metric, restore, maintenance (the forms are above, before extern "C") --
 int openr_spf_whatif_drain(openr_spf_ctx* ctx, const openr_spf_drain_events_t* events, const uint32_t* sources,
                            uint32_t n_sources, uint32_t flags, uint32_t* changed, openr_spf_whatif_delta_t* delta,
                            uint64_t* out_solved) {
-  clear_launch_trace();
-  int rc = check_drain_events(ctx, events);
-  if (rc) return rc;
-  const WhatifUnits hu = host_drain(events);
-  if ((rc = check_whatif_host(ctx, hu, sources, n_sources, changed)) != OPENR_SPF_OK) return rc;
-  if ((rc = check_drain(ctx, flags, events->n_events, n_sources)) != OPENR_SPF_OK) return rc;
-  if (!delta) return whatif_host(ctx, hu, sources, n_sources, flags, changed, out_solved);
-  return whatif_delta_host(ctx, hu, sources, n_sources, flags, changed, delta, out_solved);
+  return event_host(ctx, kElfaDrain, events, sources, n_sources, flags, changed, delta, out_solved);
 }
 
 int openr_spf_whatif_drain_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
@@ -3929,28 +4075,16 @@ int openr_spf_whatif_drain_device(openr_spf_ctx* ctx, int device_index, const ui
                                   uint32_t n_sources, uint32_t flags, uint32_t* d_changed, uint64_t* d_ptr,
                                   uint32_t* d_node, uint64_t* d_dist, uint8_t* d_nh, uint64_t cap, uint32_t nh_bytes,
                                   void* stream, uint64_t* out_total, uint64_t* out_solved) {
-  clear_launch_trace();
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (n_events && (!d_node_ptr || (n_nodes && !d_nodes) || (d_link_ptr && n_links && !d_links)))
-    return fail(OPENR_SPF_EINVAL, "null node_ptr, nodes or links");
-  int rc = check_drain(ctx, flags, n_events, n_sources);
-  if (rc) return rc;
-  return whatif_delta_device_form(ctx, device_index,
-                                  drain_units(d_node_ptr, d_nodes, d_link_ptr, d_links, n_events, n_nodes, n_links),
-                                  d_sources, n_sources, flags, d_changed, d_ptr, d_node, d_dist, d_nh, cap, nh_bytes,
-                                  stream, out_total, out_solved);
+  return event_device(ctx, device_index, drain_units(d_node_ptr, d_nodes, d_link_ptr, d_links, n_events, n_nodes, n_links),
+                      kElfaDrain, d_sources, n_sources, flags, d_changed, d_ptr, d_node, d_dist, d_nh, cap, nh_bytes,
+                      stream, out_total, out_solved);
 }
 
 int openr_spf_whatif_drain_routes(openr_spf_ctx* ctx, const openr_spf_drain_events_t* events, const uint32_t* sources,
                                   uint32_t n_sources, uint32_t flags, const openr_spf_groups_t* groups,
                                   uint32_t* changed_routes, openr_spf_whatif_routes_t* delta, uint64_t* out_solved) {
-  int rc = check_drain_events(ctx, events);
-  if (rc) return rc;
-  const WhatifUnits hu = host_drain(events);
-  if ((rc = check_whatif_host(ctx, hu, sources, n_sources, changed_routes)) != OPENR_SPF_OK) return rc;
-  if ((rc = check_drain(ctx, flags, events->n_events, n_sources)) != OPENR_SPF_OK) return rc;
-  return whatif_routes_host(ctx, hu, sources, n_sources, flags, groups, changed_routes, delta, out_solved);
+  return event_routes_host(ctx, kElfaDrain, events, sources, n_sources, flags, groups, changed_routes, delta,
+                           out_solved);
 }
 
 int openr_spf_whatif_drain_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
@@ -3962,72 +4096,16 @@ int openr_spf_whatif_drain_routes_device(openr_spf_ctx* ctx, int device_index, c
                                          uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
                                          uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes, void* stream,
                                          uint64_t* out_total, uint64_t* out_solved) {
-  clear_launch_trace();
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (device_index < 0 || device_index >= (int)ctx->devs.size())
-    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
-  if ((n_events && (!d_node_ptr || (n_nodes && !d_nodes) || (d_link_ptr && n_links && !d_links))) ||
-      (n_sources && !d_sources) || (n_events && n_sources && !d_changed_routes) || !d_ptr)
-    return fail(OPENR_SPF_EINVAL, "null events, sources, changed_routes or ptr");
-  if ((n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes))
-    return fail(OPENR_SPF_EINVAL, "null group_ptr or group_nodes");
-  if (cap && (!d_group || !d_metric || !d_nh)) return fail(OPENR_SPF_EINVAL, "null route buffer");
-  int rc = check_drain(ctx, flags, n_events, n_sources);
-  if (rc) return rc;
-  Device& d = ctx->devs[device_index];
-  HIP_TRY(hipSetDevice(d.ordinal));
-  DevGroups gr;
-  gr.ptr = d_group_ptr;
-  gr.nodes = d_group_nodes;
-  gr.n = n_groups;
-  gr.m = n_group_nodes;
-  uint64_t total = 0, solved = 0;
-  rc = whatif_routes_on_device(ctx, d, drain_units(d_node_ptr, d_nodes, d_link_ptr, d_links, n_events, n_nodes, n_links),
-                               d_sources, n_sources, flags, gr, d_changed_routes, d_ptr, d_group, d_metric, d_nh,
-                               d_n_best, cap, nh_bytes, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream,
-                               &total, &solved);
-  if (out_total) *out_total = total;
-  if (out_solved) *out_solved = solved;
-  return rc;
-}
-
-// The hop-count form of a metric sweep: metrics do not enter runSpf(src, false), so every
-// count is 0 and ptr is all zero. No kernel is launched.
-static int metric_hops_device(openr_spf_ctx* ctx, int device_index, uint32_t n_events, uint32_t n_sources,
-                              uint32_t* d_changed, uint64_t* d_ptr, void* stream, uint64_t* out_total,
-                              uint64_t* out_solved) {
-  Device& d = ctx->devs[device_index];
-  HIP_TRY(hipSetDevice(d.ordinal));
-  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : d.stream;
-  const size_t units = (size_t)n_events * n_sources;
-  if (units) HIP_TRY(hipMemsetAsync(d_changed, 0, units * sizeof(uint32_t), s));
-  HIP_TRY(hipMemsetAsync(d_ptr, 0, (units + 1) * sizeof(uint64_t), s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (out_total) *out_total = 0;
-  if (out_solved) *out_solved = 0;
-  return OPENR_SPF_OK;
+  return whatif_routes_device_form(
+      ctx, device_index, drain_units(d_node_ptr, d_nodes, d_link_ptr, d_links, n_events, n_nodes, n_links), kElfaDrain,
+      d_sources, n_sources, flags, d_group_ptr, d_group_nodes, n_groups, n_group_nodes, d_changed_routes, d_ptr, d_group,
+      d_metric, d_nh, d_n_best, cap, nh_bytes, stream, out_total, out_solved);
 }
 
 int openr_spf_whatif_metric(openr_spf_ctx* ctx, const openr_spf_metric_events_t* events, const uint32_t* sources,
                             uint32_t n_sources, uint32_t flags, uint32_t* changed, openr_spf_whatif_delta_t* delta,
                             uint64_t* out_solved) {
-  clear_launch_trace();
-  int rc = check_metric_events(ctx, events);
-  if (rc) return rc;
-  const WhatifUnits hu = host_metric(events);
-  if ((rc = check_whatif_host(ctx, hu, sources, n_sources, changed)) != OPENR_SPF_OK) return rc;
-  if ((rc = check_metric(ctx, flags, events->n_events, n_sources)) != OPENR_SPF_OK) return rc;
-  if (!(flags & OPENR_SPF_USE_LINK_METRIC)) {
-    if (delta && !delta->ptr) return fail(OPENR_SPF_EINVAL, "null delta->ptr");
-    const size_t units = (size_t)events->n_events * n_sources;
-    if (units) std::memset(changed, 0, units * sizeof(uint32_t));
-    if (delta) std::memset(delta->ptr, 0, (units + 1) * sizeof(uint64_t));
-    if (out_solved) *out_solved = 0;
-    return OPENR_SPF_OK;
-  }
-  if (!delta) return whatif_host(ctx, hu, sources, n_sources, flags, changed, out_solved);
-  return whatif_delta_host(ctx, hu, sources, n_sources, flags, changed, delta, out_solved);
+  return event_host(ctx, kElfaMetric, events, sources, n_sources, flags, changed, delta, out_solved);
 }
 
 int openr_spf_whatif_metric_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_edge_ptr,
@@ -4036,45 +4114,17 @@ int openr_spf_whatif_metric_device(openr_spf_ctx* ctx, int device_index, const u
                                    uint32_t* d_changed, uint64_t* d_ptr, uint32_t* d_node, uint64_t* d_dist,
                                    uint8_t* d_nh, uint64_t cap, uint32_t nh_bytes, void* stream, uint64_t* out_total,
                                    uint64_t* out_solved) {
-  clear_launch_trace();
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (n_events && (!d_edge_ptr || (n_edges && (!d_edges || !d_metrics))))
-    return fail(OPENR_SPF_EINVAL, "null edge_ptr, edges or metrics");
-  int rc = check_metric(ctx, flags, n_events, n_sources);
-  if (rc) return rc;
-  if (!(flags & OPENR_SPF_USE_LINK_METRIC)) {
-    if (device_index < 0 || device_index >= (int)ctx->devs.size())
-      return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
-    if ((n_sources && !d_sources) || (n_events && n_sources && !d_changed) || !d_ptr)
-      return fail(OPENR_SPF_EINVAL, "null sources, changed or ptr");
-    return metric_hops_device(ctx, device_index, n_events, n_sources, d_changed, d_ptr, stream, out_total, out_solved);
-  }
-  return whatif_delta_device_form(ctx, device_index, metric_units(d_edge_ptr, d_edges, d_metrics, n_events, n_edges),
-                                  d_sources, n_sources, flags, d_changed, d_ptr, d_node, d_dist, d_nh, cap, nh_bytes,
-                                  stream, out_total, out_solved);
+  return event_device(ctx, device_index, metric_units(d_edge_ptr, d_edges, d_metrics, n_events, n_edges), kElfaMetric,
+                      d_sources, n_sources, flags, d_changed, d_ptr, d_node, d_dist, d_nh, cap, nh_bytes, stream,
+                      out_total, out_solved);
 }
 
 int openr_spf_whatif_metric_routes(openr_spf_ctx* ctx, const openr_spf_metric_events_t* events,
                                    const uint32_t* sources, uint32_t n_sources, uint32_t flags,
                                    const openr_spf_groups_t* groups, uint32_t* changed_routes,
                                    openr_spf_whatif_routes_t* delta, uint64_t* out_solved) {
-  clear_launch_trace();
-  int rc = check_metric_events(ctx, events);
-  if (rc) return rc;
-  const WhatifUnits hu = host_metric(events);
-  if ((rc = check_whatif_host(ctx, hu, sources, n_sources, changed_routes)) != OPENR_SPF_OK) return rc;
-  if ((rc = check_metric(ctx, flags, events->n_events, n_sources)) != OPENR_SPF_OK) return rc;
-  if (!(flags & OPENR_SPF_USE_LINK_METRIC)) {
-    if ((rc = check_groups_host(ctx, groups)) != OPENR_SPF_OK) return rc;
-    if (delta && !delta->ptr) return fail(OPENR_SPF_EINVAL, "null delta->ptr");
-    const size_t units = (size_t)events->n_events * n_sources;
-    if (units) std::memset(changed_routes, 0, units * sizeof(uint32_t));
-    if (delta) std::memset(delta->ptr, 0, (units + 1) * sizeof(uint64_t));
-    if (out_solved) *out_solved = 0;
-    return OPENR_SPF_OK;
-  }
-  return whatif_routes_host(ctx, hu, sources, n_sources, flags, groups, changed_routes, delta, out_solved);
+  return event_routes_host(ctx, kElfaMetric, events, sources, n_sources, flags, groups, changed_routes, delta,
+                           out_solved);
 }
 
 int openr_spf_whatif_metric_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_edge_ptr,
@@ -4085,83 +4135,16 @@ int openr_spf_whatif_metric_routes_device(openr_spf_ctx* ctx, int device_index, 
                                           uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
                                           uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes, void* stream,
                                           uint64_t* out_total, uint64_t* out_solved) {
-  clear_launch_trace();
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (device_index < 0 || device_index >= (int)ctx->devs.size())
-    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
-  if ((n_events && (!d_edge_ptr || (n_edges && (!d_edges || !d_metrics)))) || (n_sources && !d_sources) ||
-      (n_events && n_sources && !d_changed_routes) || !d_ptr)
-    return fail(OPENR_SPF_EINVAL, "null events, sources, changed_routes or ptr");
-  if ((n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes))
-    return fail(OPENR_SPF_EINVAL, "null group_ptr or group_nodes");
-  if (cap && (!d_group || !d_metric || !d_nh)) return fail(OPENR_SPF_EINVAL, "null route buffer");
-  int rc = check_metric(ctx, flags, n_events, n_sources);
-  if (rc) return rc;
-  if (!(flags & OPENR_SPF_USE_LINK_METRIC))
-    return metric_hops_device(ctx, device_index, n_events, n_sources, d_changed_routes, d_ptr, stream, out_total,
-                              out_solved);
-  Device& d = ctx->devs[device_index];
-  HIP_TRY(hipSetDevice(d.ordinal));
-  DevGroups gr;
-  gr.ptr = d_group_ptr;
-  gr.nodes = d_group_nodes;
-  gr.n = n_groups;
-  gr.m = n_group_nodes;
-  uint64_t total = 0, solved = 0;
-  rc = whatif_routes_on_device(ctx, d, metric_units(d_edge_ptr, d_edges, d_metrics, n_events, n_edges), d_sources,
-                               n_sources, flags, gr, d_changed_routes, d_ptr, d_group, d_metric, d_nh, d_n_best, cap,
-                               nh_bytes, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream, &total, &solved);
-  if (out_total) *out_total = total;
-  if (out_solved) *out_solved = solved;
-  return rc;
-}
-
-// Host-form checks of a restore call, in the order EINVAL, the plan's ENOTSUP / E2BIG, then the
-// links whose restored edges would leave the fast plans.
-static int check_restore_host(openr_spf_ctx* ctx, const openr_spf_restore_events_t* ev, const uint32_t* sources,
-                              uint32_t n_sources, uint32_t flags, const uint32_t* changed, WhatifUnits* hu) {
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (!ev) return fail(OPENR_SPF_EINVAL, "null events");
-  if (ev->n_events && !ev->node_ptr) return fail(OPENR_SPF_EINVAL, "null node_ptr");
-  *hu = restore_units(ev->node_ptr, ev->nodes, ev->link_ptr, ev->links, ev->edge_ptr, ev->edges, ev->metrics,
-                      ev->n_events, 0u, 0u, 0u);
-  int rc = check_whatif_host(ctx, *hu, sources, n_sources, changed);
-  if (rc) return rc;
-  if ((rc = check_restore(ctx, flags, ev->n_events, n_sources)) != OPENR_SPF_OK) return rc;
-  if (!(flags & OPENR_SPF_USE_LINK_METRIC) || !hu->set_ptr) return OPENR_SPF_OK;
-  for (uint32_t i = 0; i < hu->n; ++i)
-    for (uint32_t k = hu->set_ptr[i]; k < hu->set_ptr[i + 1]; ++k) {
-      const uint2 de = ctx->ledge[hu->set_links[k]];
-      if (de.x == UINT32_MAX) continue;  // unused id
-      for (const uint32_t e : {de.x, de.y}) {
-        uint64_t m = ctx->metric[e];
-        if (hu->edge_ptr) {  // the event's own entry for e, if any
-          const uint32_t* b = hu->edges + hu->edge_ptr[i];
-          const uint32_t* en = hu->edges + hu->edge_ptr[i + 1];
-          const uint32_t* it = std::lower_bound(b, en, e);
-          if (it != en && *it == e) m = hu->metrics[it - hu->edges];
-        }
-        if (m == 0 || m > 0x7FFFFFFFull)
-          return fail(OPENR_SPF_ENOTSUP,
-                      "event %u: link %u would come up with metric %llu on edge %u, outside [1, 2^31-1] (the base "
-                      "plans after the event would need the exact-order kernel)",
-                      i, hu->set_links[k], (unsigned long long)m, e);
-      }
-    }
-  return OPENR_SPF_OK;
+  return whatif_routes_device_form(ctx, device_index, metric_units(d_edge_ptr, d_edges, d_metrics, n_events, n_edges),
+                                   kElfaMetric, d_sources, n_sources, flags, d_group_ptr, d_group_nodes, n_groups,
+                                   n_group_nodes, d_changed_routes, d_ptr, d_group, d_metric, d_nh, d_n_best, cap,
+                                   nh_bytes, stream, out_total, out_solved);
 }
 
 int openr_spf_whatif_restore(openr_spf_ctx* ctx, const openr_spf_restore_events_t* events, const uint32_t* sources,
                              uint32_t n_sources, uint32_t flags, uint32_t* changed, openr_spf_whatif_delta_t* delta,
                              uint64_t* out_solved) {
-  clear_launch_trace();
-  WhatifUnits hu;
-  int rc = check_restore_host(ctx, events, sources, n_sources, flags, changed, &hu);
-  if (rc) return rc;
-  if (!delta) return whatif_host(ctx, hu, sources, n_sources, flags, changed, out_solved);
-  return whatif_delta_host(ctx, hu, sources, n_sources, flags, changed, delta, out_solved);
+  return event_host(ctx, kElfaRestore, events, sources, n_sources, flags, changed, delta, out_solved);
 }
 
 int openr_spf_whatif_restore_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
@@ -4171,30 +4154,19 @@ int openr_spf_whatif_restore_device(openr_spf_ctx* ctx, int device_index, const 
                                     const uint32_t* d_sources, uint32_t n_sources, uint32_t flags, uint32_t* d_changed,
                                     uint64_t* d_ptr, uint32_t* d_node, uint64_t* d_dist, uint8_t* d_nh, uint64_t cap,
                                     uint32_t nh_bytes, void* stream, uint64_t* out_total, uint64_t* out_solved) {
-  clear_launch_trace();
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (n_events && (!d_node_ptr || (n_nodes && !d_nodes) || (d_link_ptr && n_links && !d_links) ||
-                   (d_edge_ptr && n_edges && (!d_edges || !d_metrics))))
-    return fail(OPENR_SPF_EINVAL, "null node_ptr, nodes, links, edges or metrics");
-  int rc = check_restore(ctx, flags, n_events, n_sources);
-  if (rc) return rc;
-  return whatif_delta_device_form(ctx, device_index,
-                                  restore_units(d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges,
-                                                d_metrics, n_events, n_nodes, n_links, n_edges),
-                                  d_sources, n_sources, flags, d_changed, d_ptr, d_node, d_dist, d_nh, cap, nh_bytes,
-                                  stream, out_total, out_solved);
+  return event_device(ctx, device_index,
+                      restore_units(d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics, n_events,
+                                    n_nodes, n_links, n_edges),
+                      kElfaRestore, d_sources, n_sources, flags, d_changed, d_ptr, d_node, d_dist, d_nh, cap, nh_bytes,
+                      stream, out_total, out_solved);
 }
 
 int openr_spf_whatif_restore_routes(openr_spf_ctx* ctx, const openr_spf_restore_events_t* events,
                                     const uint32_t* sources, uint32_t n_sources, uint32_t flags,
                                     const openr_spf_groups_t* groups, uint32_t* changed_routes,
                                     openr_spf_whatif_routes_t* delta, uint64_t* out_solved) {
-  clear_launch_trace();
-  WhatifUnits hu;
-  int rc = check_restore_host(ctx, events, sources, n_sources, flags, changed_routes, &hu);
-  if (rc) return rc;
-  return whatif_routes_host(ctx, hu, sources, n_sources, flags, groups, changed_routes, delta, out_solved);
+  return event_routes_host(ctx, kElfaRestore, events, sources, n_sources, flags, groups, changed_routes, delta,
+                           out_solved);
 }
 
 int openr_spf_whatif_restore_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
@@ -4208,61 +4180,18 @@ int openr_spf_whatif_restore_routes_device(openr_spf_ctx* ctx, int device_index,
                                            uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
                                            uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes, void* stream,
                                            uint64_t* out_total, uint64_t* out_solved) {
-  clear_launch_trace();
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (device_index < 0 || device_index >= (int)ctx->devs.size())
-    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
-  if ((n_events && (!d_node_ptr || (n_nodes && !d_nodes) || (d_link_ptr && n_links && !d_links) ||
-                    (d_edge_ptr && n_edges && (!d_edges || !d_metrics)))) ||
-      (n_sources && !d_sources) || (n_events && n_sources && !d_changed_routes) || !d_ptr)
-    return fail(OPENR_SPF_EINVAL, "null events, sources, changed_routes or ptr");
-  if ((n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes))
-    return fail(OPENR_SPF_EINVAL, "null group_ptr or group_nodes");
-  if (cap && (!d_group || !d_metric || !d_nh)) return fail(OPENR_SPF_EINVAL, "null route buffer");
-  int rc = check_restore(ctx, flags, n_events, n_sources);
-  if (rc) return rc;
-  Device& d = ctx->devs[device_index];
-  HIP_TRY(hipSetDevice(d.ordinal));
-  DevGroups gr;
-  gr.ptr = d_group_ptr;
-  gr.nodes = d_group_nodes;
-  gr.n = n_groups;
-  gr.m = n_group_nodes;
-  uint64_t total = 0, solved = 0;
-  rc = whatif_routes_on_device(ctx, d,
-                               restore_units(d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics,
-                                             n_events, n_nodes, n_links, n_edges),
-                               d_sources, n_sources, flags, gr, d_changed_routes, d_ptr, d_group, d_metric, d_nh,
-                               d_n_best, cap, nh_bytes, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream,
-                               &total, &solved);
-  if (out_total) *out_total = total;
-  if (out_solved) *out_solved = solved;
-  return rc;
-}
-
-// Host-form checks of a maintenance call, in the order EINVAL, then the plan's ENOTSUP / E2BIG.
-static int check_maint_host(openr_spf_ctx* ctx, const openr_spf_maint_events_t* ev, const uint32_t* sources,
-                            uint32_t n_sources, uint32_t flags, const uint32_t* changed, WhatifUnits* hu) {
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (!ev) return fail(OPENR_SPF_EINVAL, "null events");
-  if (ev->n_events && !ev->node_ptr) return fail(OPENR_SPF_EINVAL, "null node_ptr");
-  *hu = maint_units(ev->node_ptr, ev->nodes, ev->link_ptr, ev->links, ev->edge_ptr, ev->edges, ev->metrics,
-                    ev->n_events, 0u, 0u, 0u);
-  const int rc = check_whatif_host(ctx, *hu, sources, n_sources, changed);
-  return rc ? rc : check_maint(ctx, flags, ev->n_events, n_sources);
+  return whatif_routes_device_form(ctx, device_index,
+                                   restore_units(d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges,
+                                                 d_metrics, n_events, n_nodes, n_links, n_edges),
+                                   kElfaRestore, d_sources, n_sources, flags, d_group_ptr, d_group_nodes, n_groups,
+                                   n_group_nodes, d_changed_routes, d_ptr, d_group, d_metric, d_nh, d_n_best, cap,
+                                   nh_bytes, stream, out_total, out_solved);
 }
 
 int openr_spf_whatif_maint(openr_spf_ctx* ctx, const openr_spf_maint_events_t* events, const uint32_t* sources,
                            uint32_t n_sources, uint32_t flags, uint32_t* changed, openr_spf_whatif_delta_t* delta,
                            uint64_t* out_solved) {
-  clear_launch_trace();
-  WhatifUnits hu;
-  int rc = check_maint_host(ctx, events, sources, n_sources, flags, changed, &hu);
-  if (rc) return rc;
-  if (!delta) return whatif_host(ctx, hu, sources, n_sources, flags, changed, out_solved);
-  return whatif_delta_host(ctx, hu, sources, n_sources, flags, changed, delta, out_solved);
+  return event_host(ctx, kElfaMaint, events, sources, n_sources, flags, changed, delta, out_solved);
 }
 
 int openr_spf_whatif_maint_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
@@ -4272,30 +4201,19 @@ int openr_spf_whatif_maint_device(openr_spf_ctx* ctx, int device_index, const ui
                                   const uint32_t* d_sources, uint32_t n_sources, uint32_t flags, uint32_t* d_changed,
                                   uint64_t* d_ptr, uint32_t* d_node, uint64_t* d_dist, uint8_t* d_nh, uint64_t cap,
                                   uint32_t nh_bytes, void* stream, uint64_t* out_total, uint64_t* out_solved) {
-  clear_launch_trace();
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (n_events && (!d_node_ptr || (n_nodes && !d_nodes) || (d_link_ptr && n_links && !d_links) ||
-                   (d_edge_ptr && n_edges && (!d_edges || !d_metrics))))
-    return fail(OPENR_SPF_EINVAL, "null node_ptr, nodes, links, edges or metrics");
-  int rc = check_maint(ctx, flags, n_events, n_sources);
-  if (rc) return rc;
-  return whatif_delta_device_form(ctx, device_index,
-                                  maint_units(d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges,
-                                              d_metrics, n_events, n_nodes, n_links, n_edges),
-                                  d_sources, n_sources, flags, d_changed, d_ptr, d_node, d_dist, d_nh, cap, nh_bytes,
-                                  stream, out_total, out_solved);
+  return event_device(ctx, device_index,
+                      maint_units(d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics, n_events,
+                                  n_nodes, n_links, n_edges),
+                      kElfaMaint, d_sources, n_sources, flags, d_changed, d_ptr, d_node, d_dist, d_nh, cap, nh_bytes,
+                      stream, out_total, out_solved);
 }
 
 int openr_spf_whatif_maint_routes(openr_spf_ctx* ctx, const openr_spf_maint_events_t* events,
                                   const uint32_t* sources, uint32_t n_sources, uint32_t flags,
                                   const openr_spf_groups_t* groups, uint32_t* changed_routes,
                                   openr_spf_whatif_routes_t* delta, uint64_t* out_solved) {
-  clear_launch_trace();
-  WhatifUnits hu;
-  int rc = check_maint_host(ctx, events, sources, n_sources, flags, changed_routes, &hu);
-  if (rc) return rc;
-  return whatif_routes_host(ctx, hu, sources, n_sources, flags, groups, changed_routes, delta, out_solved);
+  return event_routes_host(ctx, kElfaMaint, events, sources, n_sources, flags, groups, changed_routes, delta,
+                           out_solved);
 }
 
 int openr_spf_whatif_maint_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
@@ -4309,37 +4227,12 @@ int openr_spf_whatif_maint_routes_device(openr_spf_ctx* ctx, int device_index, c
                                          uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
                                          uint32_t* d_n_best, uint64_t cap, uint32_t nh_bytes, void* stream,
                                          uint64_t* out_total, uint64_t* out_solved) {
-  clear_launch_trace();
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (device_index < 0 || device_index >= (int)ctx->devs.size())
-    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
-  if ((n_events && (!d_node_ptr || (n_nodes && !d_nodes) || (d_link_ptr && n_links && !d_links) ||
-                    (d_edge_ptr && n_edges && (!d_edges || !d_metrics)))) ||
-      (n_sources && !d_sources) || (n_events && n_sources && !d_changed_routes) || !d_ptr)
-    return fail(OPENR_SPF_EINVAL, "null events, sources, changed_routes or ptr");
-  if ((n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes))
-    return fail(OPENR_SPF_EINVAL, "null group_ptr or group_nodes");
-  if (cap && (!d_group || !d_metric || !d_nh)) return fail(OPENR_SPF_EINVAL, "null route buffer");
-  int rc = check_maint(ctx, flags, n_events, n_sources);
-  if (rc) return rc;
-  Device& d = ctx->devs[device_index];
-  HIP_TRY(hipSetDevice(d.ordinal));
-  DevGroups gr;
-  gr.ptr = d_group_ptr;
-  gr.nodes = d_group_nodes;
-  gr.n = n_groups;
-  gr.m = n_group_nodes;
-  uint64_t total = 0, solved = 0;
-  rc = whatif_routes_on_device(ctx, d,
-                               maint_units(d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics,
-                                           n_events, n_nodes, n_links, n_edges),
-                               d_sources, n_sources, flags, gr, d_changed_routes, d_ptr, d_group, d_metric, d_nh,
-                               d_n_best, cap, nh_bytes, stream ? reinterpret_cast<hipStream_t>(stream) : d.stream,
-                               &total, &solved);
-  if (out_total) *out_total = total;
-  if (out_solved) *out_solved = solved;
-  return rc;
+  return whatif_routes_device_form(ctx, device_index,
+                                   maint_units(d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics,
+                                               n_events, n_nodes, n_links, n_edges),
+                                   kElfaMaint, d_sources, n_sources, flags, d_group_ptr, d_group_nodes, n_groups,
+                                   n_group_nodes, d_changed_routes, d_ptr, d_group, d_metric, d_nh, d_n_best, cap,
+                                   nh_bytes, stream, out_total, out_solved);
 }
 
 int openr_spf_routes(openr_spf_ctx* ctx, const uint32_t* sources, uint32_t n, uint32_t flags,
@@ -4353,10 +4246,8 @@ int openr_spf_routes_device(openr_spf_ctx* ctx, int device_index, const uint32_t
                             uint32_t n_groups, uint32_t n_group_nodes, uint64_t* d_metric, uint8_t* d_nh,
                             uint32_t nh_bytes, uint32_t* d_n_best, void* stream) {
   clear_launch_trace();
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (device_index < 0 || device_index >= (int)ctx->devs.size())
-    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+  if (int e = check_ctx(ctx)) return e;
+  if (int e = check_device_index(ctx, device_index)) return e;
   if ((n && !d_sources) || (n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes) ||
       (n && n_groups && !d_metric))
     return fail(OPENR_SPF_EINVAL, "null sources, groups or metric");
@@ -4392,32 +4283,10 @@ int openr_spf_whatif_routes_device(openr_spf_ctx* ctx, int device_index, const u
                                    uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh, uint32_t* d_n_best,
                                    uint64_t cap, uint32_t nh_bytes, void* stream, uint64_t* out_total,
                                    uint64_t* out_solved) {
-  clear_launch_trace();
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (device_index < 0 || device_index >= (int)ctx->devs.size())
-    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
-  if ((n_sets && !d_set_ptr) || (n_sources && !d_sources) || (n_sets && n_sources && !d_changed_routes) || !d_ptr)
-    return fail(OPENR_SPF_EINVAL, "null sets, sources, changed_routes or ptr");
-  if ((n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes))
-    return fail(OPENR_SPF_EINVAL, "null group_ptr or group_nodes");
-  if (cap && (!d_group || !d_metric || !d_nh)) return fail(OPENR_SPF_EINVAL, "null route buffer");
-  int rc = check_routes_metric(ctx, flags);
-  if (rc) return rc;
-  Device& d = ctx->devs[device_index];
-  HIP_TRY(hipSetDevice(d.ordinal));
-  DevGroups gr;
-  gr.ptr = d_group_ptr;
-  gr.nodes = d_group_nodes;
-  gr.n = n_groups;
-  gr.m = n_group_nodes;
-  uint64_t total = 0, solved = 0;
-  rc = whatif_routes_on_device(ctx, d, device_sets(d_set_ptr, d_set_links, n_sets, n_set_links), d_sources, n_sources,
-                               flags, gr, d_changed_routes, d_ptr, d_group, d_metric, d_nh, d_n_best, cap, nh_bytes,
-                               stream ? reinterpret_cast<hipStream_t>(stream) : d.stream, &total, &solved);
-  if (out_total) *out_total = total;
-  if (out_solved) *out_solved = solved;
-  return rc;
+  return whatif_routes_device_form(ctx, device_index, device_sets(d_set_ptr, d_set_links, n_sets, n_set_links), -1,
+                                   d_sources, n_sources, flags, d_group_ptr, d_group_nodes, n_groups, n_group_nodes,
+                                   d_changed_routes, d_ptr, d_group, d_metric, d_nh, d_n_best, cap, nh_bytes, stream,
+                                   out_total, out_solved);
 }
 
 int openr_spf_lfa_routes(openr_spf_ctx* ctx, const uint32_t* sources, uint32_t n, uint32_t flags,
@@ -4436,10 +4305,8 @@ int openr_spf_lfa_routes_device(openr_spf_ctx* ctx, int device_index, const uint
   clear_launch_trace();
   if (out_total) *out_total = 0;
   if (out_solved) *out_solved = 0;
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (device_index < 0 || device_index >= (int)ctx->devs.size())
-    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+  if (int e = check_ctx(ctx)) return e;
+  if (int e = check_device_index(ctx, device_index)) return e;
   if ((n && !d_sources) || (n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes) ||
       (n && n_groups && !d_metric))
     return fail(OPENR_SPF_EINVAL, "null sources, groups or metric");
@@ -4492,10 +4359,8 @@ int openr_spf_whatif_lfa_device(openr_spf_ctx* ctx, int device_index, const uint
   clear_launch_trace();
   if (out_total) *out_total = 0;
   if (out_solved) *out_solved = 0;
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (device_index < 0 || device_index >= (int)ctx->devs.size())
-    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
+  if (int e = check_ctx(ctx)) return e;
+  if (int e = check_device_index(ctx, device_index)) return e;
   if ((n_sets && !d_set_ptr) || (n_sources && !d_sources) || (n_sets && n_sources && !d_changed))
     return fail(OPENR_SPF_EINVAL, "null sets, sources or changed");
   if ((n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes))
@@ -4531,68 +4396,12 @@ int openr_spf_whatif_lfa_device(openr_spf_ctx* ctx, int device_index, const uint
 }
 
 // ---- loop-free alternates under drain, metric, restore and maintenance events (spf_elfa.hip) --
-
-// The family's capacity check for a call whose only E2BIG is "sum(changed) > cap": a graph
-// whose repair unit does not fit LDS is not supported by these calls.
-static int event_lfa_check(int rc) {
-  return rc == OPENR_SPF_E2BIG ? OPENR_SPF_ENOTSUP : rc;
-}
-
-// The device forms behind their event arguments (un: events of ElfaFamily fam in device memory).
-static int event_lfa_device(openr_spf_ctx* ctx, int device_index, const WhatifUnits& un, int fam,
-                            const uint32_t* d_sources, uint32_t n_sources, uint32_t flags,
-                            const uint32_t* d_group_ptr, const uint32_t* d_group_nodes, uint32_t n_groups,
-                            uint32_t n_group_nodes, uint32_t* d_changed, uint32_t* d_unprotected,
-                            uint32_t* d_lost_backup, uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric,
-                            uint8_t* d_nh, uint8_t* d_alt, uint64_t cap, uint32_t nh_bytes, void* stream,
-                            uint64_t* out_total, uint64_t* out_solved) {
-  if (device_index < 0 || device_index >= (int)ctx->devs.size())
-    return fail(OPENR_SPF_EINVAL, "device_index %d out of range", device_index);
-  if ((n_sources && !d_sources) || (un.n && n_sources && !d_changed))
-    return fail(OPENR_SPF_EINVAL, "null sources or changed");
-  if ((n_groups && !d_group_ptr) || (n_group_nodes && !d_group_nodes))
-    return fail(OPENR_SPF_EINVAL, "null group_ptr or group_nodes");
-  if (cap && (!d_ptr || !d_group || !d_metric || !d_nh || !d_alt)) return fail(OPENR_SPF_EINVAL, "null entry buffer");
-  int rc = check_routes_metric(ctx, flags);
-  if (rc) return rc;
-  Device& d = ctx->devs[device_index];
-  HIP_TRY(hipSetDevice(d.ordinal));
-  DevGroups gr;
-  gr.ptr = d_group_ptr;
-  gr.nodes = d_group_nodes;
-  gr.n = n_groups;
-  gr.m = n_group_nodes;
-  WlfaOut out;
-  out.changed = d_changed;
-  out.unprot = d_unprotected;
-  out.lost = d_lost_backup;
-  out.ptr = d_ptr;
-  out.group = d_group;
-  out.metric = d_metric;
-  out.nh = d_nh;
-  out.alt = d_alt;
-  out.cap = cap;
-  out.nhb = nh_bytes;
-  uint64_t total = 0, solved = 0;
-  rc = whatif_lfa_on_device(ctx, d, un, d_sources, n_sources, flags, gr, out,
-                            stream ? reinterpret_cast<hipStream_t>(stream) : d.stream, &total, &solved, fam);
-  if (out_total) *out_total = total;
-  if (out_solved) *out_solved = solved;
-  return rc;
-}
-
 int openr_spf_whatif_drain_lfa(openr_spf_ctx* ctx, const openr_spf_drain_events_t* events, const uint32_t* sources,
                                uint32_t n_sources, uint32_t flags, const openr_spf_groups_t* groups,
                                uint32_t* changed, uint32_t* unprotected, uint32_t* lost_backup,
                                openr_spf_whatif_lfa_t* delta, uint64_t* out_solved) {
-  if (out_solved) *out_solved = 0;
-  int rc = check_drain_events(ctx, events);
-  if (rc) return rc;
-  const WhatifUnits hu = host_drain(events);
-  if ((rc = check_whatif_host(ctx, hu, sources, n_sources, changed)) != OPENR_SPF_OK) return rc;
-  if ((rc = event_lfa_check(check_drain(ctx, flags, events->n_events, n_sources))) != OPENR_SPF_OK) return rc;
-  return whatif_lfa_host(ctx, hu, sources, n_sources, flags, groups, changed, unprotected, lost_backup, delta,
-                         out_solved, kElfaDrain);
+  return event_lfa_host(ctx, kElfaDrain, events, sources, n_sources, flags, groups, changed, unprotected, lost_backup,
+                        delta, out_solved);
 }
 
 int openr_spf_whatif_drain_lfa_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
@@ -4604,15 +4413,6 @@ int openr_spf_whatif_drain_lfa_device(openr_spf_ctx* ctx, int device_index, cons
                                       uint32_t* d_lost_backup, uint64_t* d_ptr, uint32_t* d_group,
                                       uint64_t* d_metric, uint8_t* d_nh, uint8_t* d_alt, uint64_t cap,
                                       uint32_t nh_bytes, void* stream, uint64_t* out_total, uint64_t* out_solved) {
-  clear_launch_trace();
-  if (out_total) *out_total = 0;
-  if (out_solved) *out_solved = 0;
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (n_events && (!d_node_ptr || (n_nodes && !d_nodes) || (d_link_ptr && n_links && !d_links)))
-    return fail(OPENR_SPF_EINVAL, "null node_ptr, nodes or links");
-  const int rc = event_lfa_check(check_drain(ctx, flags, n_events, n_sources));
-  if (rc) return rc;
   return event_lfa_device(ctx, device_index,
                           drain_units(d_node_ptr, d_nodes, d_link_ptr, d_links, n_events, n_nodes, n_links),
                           kElfaDrain, d_sources, n_sources, flags, d_group_ptr, d_group_nodes, n_groups,
@@ -4624,14 +4424,8 @@ int openr_spf_whatif_metric_lfa(openr_spf_ctx* ctx, const openr_spf_metric_event
                                 uint32_t n_sources, uint32_t flags, const openr_spf_groups_t* groups,
                                 uint32_t* changed, uint32_t* unprotected, uint32_t* lost_backup,
                                 openr_spf_whatif_lfa_t* delta, uint64_t* out_solved) {
-  if (out_solved) *out_solved = 0;
-  int rc = check_metric_events(ctx, events);
-  if (rc) return rc;
-  const WhatifUnits hu = host_metric(events);
-  if ((rc = check_whatif_host(ctx, hu, sources, n_sources, changed)) != OPENR_SPF_OK) return rc;
-  if ((rc = event_lfa_check(check_metric(ctx, flags, events->n_events, n_sources))) != OPENR_SPF_OK) return rc;
-  return whatif_lfa_host(ctx, hu, sources, n_sources, flags, groups, changed, unprotected, lost_backup, delta,
-                         out_solved, kElfaMetric);
+  return event_lfa_host(ctx, kElfaMetric, events, sources, n_sources, flags, groups, changed, unprotected, lost_backup,
+                        delta, out_solved);
 }
 
 int openr_spf_whatif_metric_lfa_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_edge_ptr,
@@ -4643,15 +4437,6 @@ int openr_spf_whatif_metric_lfa_device(openr_spf_ctx* ctx, int device_index, con
                                        uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh, uint8_t* d_alt,
                                        uint64_t cap, uint32_t nh_bytes, void* stream, uint64_t* out_total,
                                        uint64_t* out_solved) {
-  clear_launch_trace();
-  if (out_total) *out_total = 0;
-  if (out_solved) *out_solved = 0;
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (n_events && (!d_edge_ptr || (n_edges && (!d_edges || !d_metrics))))
-    return fail(OPENR_SPF_EINVAL, "null edge_ptr, edges or metrics");
-  const int rc = event_lfa_check(check_metric(ctx, flags, n_events, n_sources));
-  if (rc) return rc;
   return event_lfa_device(ctx, device_index, metric_units(d_edge_ptr, d_edges, d_metrics, n_events, n_edges),
                           kElfaMetric, d_sources, n_sources, flags, d_group_ptr, d_group_nodes, n_groups,
                           n_group_nodes, d_changed, d_unprotected, d_lost_backup, d_ptr, d_group, d_metric, d_nh,
@@ -4662,12 +4447,8 @@ int openr_spf_whatif_restore_lfa(openr_spf_ctx* ctx, const openr_spf_restore_eve
                                  const uint32_t* sources, uint32_t n_sources, uint32_t flags,
                                  const openr_spf_groups_t* groups, uint32_t* changed, uint32_t* unprotected,
                                  uint32_t* lost_backup, openr_spf_whatif_lfa_t* delta, uint64_t* out_solved) {
-  if (out_solved) *out_solved = 0;
-  WhatifUnits hu;
-  const int rc = event_lfa_check(check_restore_host(ctx, events, sources, n_sources, flags, changed, &hu));
-  if (rc) return rc;
-  return whatif_lfa_host(ctx, hu, sources, n_sources, flags, groups, changed, unprotected, lost_backup, delta,
-                         out_solved, kElfaRestore);
+  return event_lfa_host(ctx, kElfaRestore, events, sources, n_sources, flags, groups, changed, unprotected,
+                        lost_backup, delta, out_solved);
 }
 
 int openr_spf_whatif_restore_lfa_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
@@ -4681,16 +4462,6 @@ int openr_spf_whatif_restore_lfa_device(openr_spf_ctx* ctx, int device_index, co
                                         uint64_t* d_ptr, uint32_t* d_group, uint64_t* d_metric, uint8_t* d_nh,
                                         uint8_t* d_alt, uint64_t cap, uint32_t nh_bytes, void* stream,
                                         uint64_t* out_total, uint64_t* out_solved) {
-  clear_launch_trace();
-  if (out_total) *out_total = 0;
-  if (out_solved) *out_solved = 0;
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (n_events && (!d_node_ptr || (n_nodes && !d_nodes) || (d_link_ptr && n_links && !d_links) ||
-                   (d_edge_ptr && n_edges && (!d_edges || !d_metrics))))
-    return fail(OPENR_SPF_EINVAL, "null node_ptr, nodes, links, edges or metrics");
-  const int rc = event_lfa_check(check_restore(ctx, flags, n_events, n_sources));
-  if (rc) return rc;
   return event_lfa_device(ctx, device_index,
                           restore_units(d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics,
                                         n_events, n_nodes, n_links, n_edges),
@@ -4705,12 +4476,8 @@ int openr_spf_whatif_maint_lfa(openr_spf_ctx* ctx, const openr_spf_maint_events_
                                uint32_t n_sources, uint32_t flags, const openr_spf_groups_t* groups,
                                uint32_t* changed, uint32_t* unprotected, uint32_t* lost_backup,
                                openr_spf_whatif_lfa_t* delta, uint64_t* out_solved) {
-  if (out_solved) *out_solved = 0;
-  WhatifUnits hu;
-  const int rc = event_lfa_check(check_maint_host(ctx, events, sources, n_sources, flags, changed, &hu));
-  if (rc) return rc;
-  return whatif_lfa_host(ctx, hu, sources, n_sources, flags, groups, changed, unprotected, lost_backup, delta,
-                         out_solved, kElfaMaint);
+  return event_lfa_host(ctx, kElfaMaint, events, sources, n_sources, flags, groups, changed, unprotected, lost_backup,
+                        delta, out_solved);
 }
 
 int openr_spf_whatif_maint_lfa_device(openr_spf_ctx* ctx, int device_index, const uint32_t* d_node_ptr,
@@ -4723,16 +4490,6 @@ int openr_spf_whatif_maint_lfa_device(openr_spf_ctx* ctx, int device_index, cons
                                       uint32_t* d_lost_backup, uint64_t* d_ptr, uint32_t* d_group,
                                       uint64_t* d_metric, uint8_t* d_nh, uint8_t* d_alt, uint64_t cap,
                                       uint32_t nh_bytes, void* stream, uint64_t* out_total, uint64_t* out_solved) {
-  clear_launch_trace();
-  if (out_total) *out_total = 0;
-  if (out_solved) *out_solved = 0;
-  if (!ctx) return fail(OPENR_SPF_EINVAL, "null context");
-  if (!ctx->has_graph) return fail(OPENR_SPF_EINVAL, "no graph set (openr_spf_set_graph)");
-  if (n_events && (!d_node_ptr || (n_nodes && !d_nodes) || (d_link_ptr && n_links && !d_links) ||
-                   (d_edge_ptr && n_edges && (!d_edges || !d_metrics))))
-    return fail(OPENR_SPF_EINVAL, "null node_ptr, nodes, links, edges or metrics");
-  const int rc = event_lfa_check(check_maint(ctx, flags, n_events, n_sources));
-  if (rc) return rc;
   return event_lfa_device(ctx, device_index,
                           maint_units(d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics,
                                       n_events, n_nodes, n_links, n_edges),

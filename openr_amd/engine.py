@@ -830,6 +830,93 @@ class SpfEngine:
             _check(rc)
         return int(total.value), int(solved.value)
 
+    # ---- the event sweeps: one body per call form; a family gives its C function and its events ----
+    def _event_sweep(self, fn, ev, n: int, sources, use_link_metric, want_delta, cap, nh_bytes):
+        """The host call ``fn`` over the events ``ev`` (n of them): the tuple whatif_sets_delta
+        returns, or (changed, solved) with want_delta False. cap None: sized from a count-only pass."""
+        src = np.ascontiguousarray(sources, dtype=np.uint32)
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
+        solved = ctypes.c_uint64()
+
+        def call(d):
+            return fn(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags, _p(changed), d, ctypes.byref(solved))
+
+        if not want_delta or cap is None:
+            _check(call(None))
+            if not want_delta:
+                return changed, int(solved.value)
+            cap = int(changed.sum(dtype=np.uint64))
+        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
+        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
+        node = np.zeros(max(cap, 1), dtype=np.uint32)
+        dist = np.zeros(max(cap, 1), dtype=np.uint64)
+        nh = np.zeros((max(cap, 1), nb), dtype=np.uint8)
+        d = WhatifDelta(_p(ptr), _p(node), _p(dist), _p(nh), cap, nb)
+        _check(call(ctypes.byref(d)))
+        k = int(ptr[-1])
+        return changed, ptr, node[:k], dist[:k], nh[:k], int(solved.value)
+
+    def _event_routes(self, fn, ev, n: int, sources, groups, use_link_metric, cap, nh_bytes):
+        """The host call ``fn`` over the events ``ev`` (n of them): the tuple whatif_routes returns."""
+        gp, gn = _ignore_arrays(groups, len(groups))
+        gs = SpfGroups(len(groups), _p(gp), _p(gn))
+        src = np.ascontiguousarray(sources, dtype=np.uint32)
+        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
+        solved = ctypes.c_uint64()
+
+        def call(d):
+            return fn(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags, ctypes.byref(gs), _p(changed), d,
+                      ctypes.byref(solved))
+
+        if cap is None:
+            _check(call(None))
+            cap = int(changed.sum(dtype=np.uint64))
+        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
+        group = np.zeros(max(cap, 1), dtype=np.uint32)
+        metric = np.zeros(max(cap, 1), dtype=np.uint64)
+        nh = np.zeros((max(cap, 1), nb), dtype=np.uint8)
+        n_best = np.zeros(max(cap, 1), dtype=np.uint32)
+        d = WhatifRoutes(_p(ptr), _p(group), _p(metric), _p(nh), _p(n_best), cap, nb)
+        _check(call(ctypes.byref(d)))
+        k = int(ptr[-1])
+        return changed, ptr, group[:k], metric[:k], nh[:k], n_best[:k], int(solved.value)
+
+    def _event_device(self, fn, event_args, d_sources, n_sources, d_changed, d_ptr, d_node, d_dist, d_nh, cap,
+                      nh_bytes, use_link_metric, stream, device_index, allow_overflow) -> Tuple[int, int]:
+        vp = ctypes.c_void_p
+        total = ctypes.c_uint64()
+        solved = ctypes.c_uint64()
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        rc = fn(self._ctx, device_index, *event_args, vp(d_sources), n_sources, flags, vp(d_changed), vp(d_ptr),
+                vp(d_node or None), vp(d_dist or None), vp(d_nh or None), cap, nh_bytes, vp(stream or None),
+                ctypes.byref(total), ctypes.byref(solved))
+        if not (allow_overflow and rc == E2BIG):
+            _check(rc)
+        return int(total.value), int(solved.value)
+
+    def _event_routes_device(self, fn, event_args, d_sources, n_sources, d_group_ptr, d_group_nodes, n_groups,
+                             n_group_nodes, d_changed, d_ptr, d_group, d_metric, d_nh, d_n_best, cap, nh_bytes,
+                             use_link_metric, stream, device_index, allow_overflow) -> Tuple[int, int]:
+        vp = ctypes.c_void_p
+        total = ctypes.c_uint64()
+        solved = ctypes.c_uint64()
+        flags = USE_LINK_METRIC if use_link_metric else 0
+        rc = fn(self._ctx, device_index, *event_args, vp(d_sources), n_sources, flags, vp(d_group_ptr or None),
+                vp(d_group_nodes or None), n_groups, n_group_nodes, vp(d_changed), vp(d_ptr), vp(d_group or None),
+                vp(d_metric or None), vp(d_nh or None), vp(d_n_best or None), cap, nh_bytes, vp(stream or None),
+                ctypes.byref(total), ctypes.byref(solved))
+        if not (allow_overflow and rc == E2BIG):
+            _check(rc)
+        return int(total.value), int(solved.value)
+
+    @staticmethod
+    def _device_events(addresses, *counts):
+        """The leading event arguments of a device form: the CSR addresses (0: NULL), then the counts."""
+        return tuple(ctypes.c_void_p(a or None) for a in addresses) + counts
+
     @staticmethod
     def _drain_events(node_sets: Sequence[Sequence[int]], link_sets: Optional[Sequence[Sequence[int]]]):
         """(DrainEvents, the arrays it points into) of per-event node and link lists."""
@@ -849,28 +936,10 @@ class SpfEngine:
         solved), or (changed, solved) with want_delta=False. cap None: sized from a count-only
         pass."""
         ev, keep = self._drain_events(node_sets, link_sets)
-        n = len(node_sets)
-        src = np.ascontiguousarray(sources, dtype=np.uint32)
-        flags = USE_LINK_METRIC if use_link_metric else 0
-        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
-        solved = ctypes.c_uint64()
-        if not want_delta or cap is None:
-            _check(self._lib.openr_spf_whatif_drain(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
-                                                    _p(changed), None, ctypes.byref(solved)))
-            if not want_delta:
-                return changed, int(solved.value)
-            cap = int(changed.sum(dtype=np.uint64))
-        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
-        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
-        node = np.zeros(max(cap, 1), dtype=np.uint32)
-        dist = np.zeros(max(cap, 1), dtype=np.uint64)
-        nh = np.zeros((max(cap, 1), nb), dtype=np.uint8)
-        d = WhatifDelta(_p(ptr), _p(node), _p(dist), _p(nh), cap, nb)
-        _check(self._lib.openr_spf_whatif_drain(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
-                                                _p(changed), ctypes.byref(d), ctypes.byref(solved)))
+        out = self._event_sweep(self._lib.openr_spf_whatif_drain, ev, len(node_sets), sources, use_link_metric,
+                              want_delta, cap, nh_bytes)
         del keep
-        k = int(ptr[-1])
-        return changed, ptr, node[:k], dist[:k], nh[:k], int(solved.value)
+        return out
 
     def whatif_drain_device(self, d_node_ptr: int, d_nodes: int, d_link_ptr: int, d_links: int, n_events: int,
                             n_nodes: int, n_links: int, d_sources: int, n_sources: int, d_changed: int, d_ptr: int,
@@ -879,18 +948,10 @@ class SpfEngine:
                             allow_overflow: bool = False) -> Tuple[int, int]:
         """Device-pointer form: (total entries, solved). d_link_ptr 0: no links. d_ptr
         [n_units + 1] u64 CSR; unit u's entries are [ptr[u], ptr[u + 1]) in the kernel's order."""
-        vp = ctypes.c_void_p
-        total = ctypes.c_uint64()
-        solved = ctypes.c_uint64()
-        flags = USE_LINK_METRIC if use_link_metric else 0
-        rc = self._lib.openr_spf_whatif_drain_device(
-            self._ctx, device_index, vp(d_node_ptr or None), vp(d_nodes or None), vp(d_link_ptr or None),
-            vp(d_links or None), n_events, n_nodes, n_links, vp(d_sources), n_sources, flags, vp(d_changed), vp(d_ptr),
-            vp(d_node or None), vp(d_dist or None), vp(d_nh or None), cap, nh_bytes, vp(stream or None),
-            ctypes.byref(total), ctypes.byref(solved))
-        if not (allow_overflow and rc == E2BIG):
-            _check(rc)
-        return int(total.value), int(solved.value)
+        ev = self._device_events((d_node_ptr, d_nodes, d_link_ptr, d_links), n_events, n_nodes, n_links)
+        return self._event_device(self._lib.openr_spf_whatif_drain_device, ev, d_sources, n_sources, d_changed, d_ptr,
+                                  d_node, d_dist, d_nh, cap, nh_bytes, use_link_metric, stream, device_index,
+                                  allow_overflow)
 
     def whatif_drain_routes(self, node_sets: Sequence[Sequence[int]], sources: Sequence[int],
                             groups: Sequence[Sequence[int]], link_sets: Optional[Sequence[Sequence[int]]] = None,
@@ -899,30 +960,10 @@ class SpfEngine:
         """The drain sweep resolved to routes (openr_spf_whatif_drain_routes): the return shape
         of whatif_routes. cap None: sized from a count-only pass."""
         ev, keep = self._drain_events(node_sets, link_sets)
-        n = len(node_sets)
-        gp, gn = _ignore_arrays(groups, len(groups))
-        gs = SpfGroups(len(groups), _p(gp), _p(gn))
-        src = np.ascontiguousarray(sources, dtype=np.uint32)
-        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
-        flags = USE_LINK_METRIC if use_link_metric else 0
-        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
-        solved = ctypes.c_uint64()
-        if cap is None:
-            _check(self._lib.openr_spf_whatif_drain_routes(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
-                                                           ctypes.byref(gs), _p(changed), None, ctypes.byref(solved)))
-            cap = int(changed.sum(dtype=np.uint64))
-        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
-        group = np.zeros(max(cap, 1), dtype=np.uint32)
-        metric = np.zeros(max(cap, 1), dtype=np.uint64)
-        nh = np.zeros((max(cap, 1), nb), dtype=np.uint8)
-        n_best = np.zeros(max(cap, 1), dtype=np.uint32)
-        d = WhatifRoutes(_p(ptr), _p(group), _p(metric), _p(nh), _p(n_best), cap, nb)
-        _check(self._lib.openr_spf_whatif_drain_routes(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
-                                                       ctypes.byref(gs), _p(changed), ctypes.byref(d),
-                                                       ctypes.byref(solved)))
+        out = self._event_routes(self._lib.openr_spf_whatif_drain_routes, ev, len(node_sets), sources, groups,
+                               use_link_metric, cap, nh_bytes)
         del keep
-        k = int(ptr[-1])
-        return changed, ptr, group[:k], metric[:k], nh[:k], n_best[:k], int(solved.value)
+        return out
 
     def whatif_drain_routes_device(self, d_node_ptr: int, d_nodes: int, d_link_ptr: int, d_links: int, n_events: int,
                                    n_nodes: int, n_links: int, d_sources: int, n_sources: int, d_group_ptr: int,
@@ -931,19 +972,11 @@ class SpfEngine:
                                    use_link_metric: bool = True, stream: int = 0, device_index: int = 0,
                                    allow_overflow: bool = False) -> Tuple[int, int]:
         """Device-pointer form: (total entries, solved); outputs as whatif_routes_device."""
-        vp = ctypes.c_void_p
-        total = ctypes.c_uint64()
-        solved = ctypes.c_uint64()
-        flags = USE_LINK_METRIC if use_link_metric else 0
-        rc = self._lib.openr_spf_whatif_drain_routes_device(
-            self._ctx, device_index, vp(d_node_ptr or None), vp(d_nodes or None), vp(d_link_ptr or None),
-            vp(d_links or None), n_events, n_nodes, n_links, vp(d_sources), n_sources, flags,
-            vp(d_group_ptr or None), vp(d_group_nodes or None), n_groups, n_group_nodes, vp(d_changed), vp(d_ptr),
-            vp(d_group or None), vp(d_metric or None), vp(d_nh or None), vp(d_n_best or None), cap, nh_bytes,
-            vp(stream or None), ctypes.byref(total), ctypes.byref(solved))
-        if not (allow_overflow and rc == E2BIG):
-            _check(rc)
-        return int(total.value), int(solved.value)
+        ev = self._device_events((d_node_ptr, d_nodes, d_link_ptr, d_links), n_events, n_nodes, n_links)
+        return self._event_routes_device(self._lib.openr_spf_whatif_drain_routes_device, ev, d_sources, n_sources,
+                                         d_group_ptr, d_group_nodes, n_groups, n_group_nodes, d_changed, d_ptr,
+                                         d_group, d_metric, d_nh, d_n_best, cap, nh_bytes, use_link_metric, stream,
+                                         device_index, allow_overflow)
 
     @staticmethod
     def _metric_events(edge_sets: Sequence[Sequence[int]], metric_sets: Sequence[Sequence[int]]):
@@ -965,28 +998,10 @@ class SpfEngine:
         shape of whatif_drain: (changed[n_events, n_sources] u32, ptr, node, dist, nh, solved),
         or (changed, solved) with want_delta=False. cap None: sized from a count-only pass."""
         ev, keep = self._metric_events(edge_sets, metric_sets)
-        n = len(edge_sets)
-        src = np.ascontiguousarray(sources, dtype=np.uint32)
-        flags = USE_LINK_METRIC if use_link_metric else 0
-        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
-        solved = ctypes.c_uint64()
-        if not want_delta or cap is None:
-            _check(self._lib.openr_spf_whatif_metric(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
-                                                     _p(changed), None, ctypes.byref(solved)))
-            if not want_delta:
-                return changed, int(solved.value)
-            cap = int(changed.sum(dtype=np.uint64))
-        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
-        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
-        node = np.zeros(max(cap, 1), dtype=np.uint32)
-        dist = np.zeros(max(cap, 1), dtype=np.uint64)
-        nh = np.zeros((max(cap, 1), nb), dtype=np.uint8)
-        d = WhatifDelta(_p(ptr), _p(node), _p(dist), _p(nh), cap, nb)
-        _check(self._lib.openr_spf_whatif_metric(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
-                                                 _p(changed), ctypes.byref(d), ctypes.byref(solved)))
+        out = self._event_sweep(self._lib.openr_spf_whatif_metric, ev, len(edge_sets), sources, use_link_metric,
+                              want_delta, cap, nh_bytes)
         del keep
-        k = int(ptr[-1])
-        return changed, ptr, node[:k], dist[:k], nh[:k], int(solved.value)
+        return out
 
     def whatif_metric_device(self, d_edge_ptr: int, d_edges: int, d_metrics: int, n_events: int, n_edges: int,
                              d_sources: int, n_sources: int, d_changed: int, d_ptr: int, d_node: int, d_dist: int,
@@ -994,18 +1009,10 @@ class SpfEngine:
                              device_index: int = 0, allow_overflow: bool = False) -> Tuple[int, int]:
         """Device-pointer form: (total entries, solved). d_ptr [n_units + 1] u64 CSR; unit u's
         entries are [ptr[u], ptr[u + 1]) in the kernel's order."""
-        vp = ctypes.c_void_p
-        total = ctypes.c_uint64()
-        solved = ctypes.c_uint64()
-        flags = USE_LINK_METRIC if use_link_metric else 0
-        rc = self._lib.openr_spf_whatif_metric_device(
-            self._ctx, device_index, vp(d_edge_ptr or None), vp(d_edges or None), vp(d_metrics or None), n_events,
-            n_edges, vp(d_sources), n_sources, flags, vp(d_changed), vp(d_ptr), vp(d_node or None),
-            vp(d_dist or None), vp(d_nh or None), cap, nh_bytes, vp(stream or None), ctypes.byref(total),
-            ctypes.byref(solved))
-        if not (allow_overflow and rc == E2BIG):
-            _check(rc)
-        return int(total.value), int(solved.value)
+        ev = self._device_events((d_edge_ptr, d_edges, d_metrics), n_events, n_edges)
+        return self._event_device(self._lib.openr_spf_whatif_metric_device, ev, d_sources, n_sources, d_changed,
+                                  d_ptr, d_node, d_dist, d_nh, cap, nh_bytes, use_link_metric, stream, device_index,
+                                  allow_overflow)
 
     def whatif_metric_routes(self, edge_sets: Sequence[Sequence[int]], metric_sets: Sequence[Sequence[int]],
                              sources: Sequence[int], groups: Sequence[Sequence[int]], use_link_metric: bool = True,
@@ -1013,30 +1020,10 @@ class SpfEngine:
         """The metric sweep resolved to routes (openr_spf_whatif_metric_routes): the return shape
         of whatif_routes. cap None: sized from a count-only pass."""
         ev, keep = self._metric_events(edge_sets, metric_sets)
-        n = len(edge_sets)
-        gp, gn = _ignore_arrays(groups, len(groups))
-        gs = SpfGroups(len(groups), _p(gp), _p(gn))
-        src = np.ascontiguousarray(sources, dtype=np.uint32)
-        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
-        flags = USE_LINK_METRIC if use_link_metric else 0
-        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
-        solved = ctypes.c_uint64()
-        if cap is None:
-            _check(self._lib.openr_spf_whatif_metric_routes(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
-                                                            ctypes.byref(gs), _p(changed), None, ctypes.byref(solved)))
-            cap = int(changed.sum(dtype=np.uint64))
-        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
-        group = np.zeros(max(cap, 1), dtype=np.uint32)
-        metric = np.zeros(max(cap, 1), dtype=np.uint64)
-        nh = np.zeros((max(cap, 1), nb), dtype=np.uint8)
-        n_best = np.zeros(max(cap, 1), dtype=np.uint32)
-        d = WhatifRoutes(_p(ptr), _p(group), _p(metric), _p(nh), _p(n_best), cap, nb)
-        _check(self._lib.openr_spf_whatif_metric_routes(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
-                                                        ctypes.byref(gs), _p(changed), ctypes.byref(d),
-                                                        ctypes.byref(solved)))
+        out = self._event_routes(self._lib.openr_spf_whatif_metric_routes, ev, len(edge_sets), sources, groups,
+                               use_link_metric, cap, nh_bytes)
         del keep
-        k = int(ptr[-1])
-        return changed, ptr, group[:k], metric[:k], nh[:k], n_best[:k], int(solved.value)
+        return out
 
     def whatif_metric_routes_device(self, d_edge_ptr: int, d_edges: int, d_metrics: int, n_events: int, n_edges: int,
                                     d_sources: int, n_sources: int, d_group_ptr: int, d_group_nodes: int,
@@ -1045,18 +1032,11 @@ class SpfEngine:
                                     use_link_metric: bool = True, stream: int = 0, device_index: int = 0,
                                     allow_overflow: bool = False) -> Tuple[int, int]:
         """Device-pointer form: (total entries, solved); outputs as whatif_routes_device."""
-        vp = ctypes.c_void_p
-        total = ctypes.c_uint64()
-        solved = ctypes.c_uint64()
-        flags = USE_LINK_METRIC if use_link_metric else 0
-        rc = self._lib.openr_spf_whatif_metric_routes_device(
-            self._ctx, device_index, vp(d_edge_ptr or None), vp(d_edges or None), vp(d_metrics or None), n_events,
-            n_edges, vp(d_sources), n_sources, flags, vp(d_group_ptr or None), vp(d_group_nodes or None), n_groups,
-            n_group_nodes, vp(d_changed), vp(d_ptr), vp(d_group or None), vp(d_metric or None), vp(d_nh or None),
-            vp(d_n_best or None), cap, nh_bytes, vp(stream or None), ctypes.byref(total), ctypes.byref(solved))
-        if not (allow_overflow and rc == E2BIG):
-            _check(rc)
-        return int(total.value), int(solved.value)
+        ev = self._device_events((d_edge_ptr, d_edges, d_metrics), n_events, n_edges)
+        return self._event_routes_device(self._lib.openr_spf_whatif_metric_routes_device, ev, d_sources, n_sources,
+                                         d_group_ptr, d_group_nodes, n_groups, n_group_nodes, d_changed, d_ptr,
+                                         d_group, d_metric, d_nh, d_n_best, cap, nh_bytes, use_link_metric, stream,
+                                         device_index, allow_overflow)
 
     @staticmethod
     def _restore_events(node_sets, link_sets, edge_sets, metric_sets, struct=RestoreEvents):
@@ -1090,27 +1070,10 @@ class SpfEngine:
         whatif_metric: (changed[n_events, n_sources] u32, ptr, node, dist, nh, solved), or
         (changed, solved) with want_delta=False. cap None: sized from a count-only pass."""
         ev, keep, n = self._restore_events(node_sets, link_sets, edge_sets, metric_sets)
-        src = np.ascontiguousarray(sources, dtype=np.uint32)
-        flags = USE_LINK_METRIC if use_link_metric else 0
-        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
-        solved = ctypes.c_uint64()
-        if not want_delta or cap is None:
-            _check(self._lib.openr_spf_whatif_restore(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
-                                                      _p(changed), None, ctypes.byref(solved)))
-            if not want_delta:
-                return changed, int(solved.value)
-            cap = int(changed.sum(dtype=np.uint64))
-        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
-        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
-        node = np.zeros(max(cap, 1), dtype=np.uint32)
-        dist = np.zeros(max(cap, 1), dtype=np.uint64)
-        nh = np.zeros((max(cap, 1), nb), dtype=np.uint8)
-        d = WhatifDelta(_p(ptr), _p(node), _p(dist), _p(nh), cap, nb)
-        _check(self._lib.openr_spf_whatif_restore(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
-                                                  _p(changed), ctypes.byref(d), ctypes.byref(solved)))
+        out = self._event_sweep(self._lib.openr_spf_whatif_restore, ev, n, sources, use_link_metric, want_delta, cap,
+                              nh_bytes)
         del keep
-        k = int(ptr[-1])
-        return changed, ptr, node[:k], dist[:k], nh[:k], int(solved.value)
+        return out
 
     def whatif_restore_device(self, d_node_ptr: int, d_nodes: int, d_link_ptr: int, d_links: int, d_edge_ptr: int,
                               d_edges: int, d_metrics: int, n_events: int, n_nodes: int, n_links: int, n_edges: int,
@@ -1120,19 +1083,11 @@ class SpfEngine:
         """Device-pointer form: (total entries, solved). d_link_ptr / d_edge_ptr 0: no links /
         no metric entries. d_ptr [n_units + 1] u64 CSR; unit u's entries are [ptr[u],
         ptr[u + 1]) in the kernel's order."""
-        vp = ctypes.c_void_p
-        total = ctypes.c_uint64()
-        solved = ctypes.c_uint64()
-        flags = USE_LINK_METRIC if use_link_metric else 0
-        rc = self._lib.openr_spf_whatif_restore_device(
-            self._ctx, device_index, vp(d_node_ptr or None), vp(d_nodes or None), vp(d_link_ptr or None),
-            vp(d_links or None), vp(d_edge_ptr or None), vp(d_edges or None), vp(d_metrics or None), n_events, n_nodes,
-            n_links, n_edges, vp(d_sources), n_sources, flags, vp(d_changed), vp(d_ptr), vp(d_node or None),
-            vp(d_dist or None), vp(d_nh or None), cap, nh_bytes, vp(stream or None), ctypes.byref(total),
-            ctypes.byref(solved))
-        if not (allow_overflow and rc == E2BIG):
-            _check(rc)
-        return int(total.value), int(solved.value)
+        ev = self._device_events((d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics), n_events,
+                                 n_nodes, n_links, n_edges)
+        return self._event_device(self._lib.openr_spf_whatif_restore_device, ev, d_sources, n_sources, d_changed,
+                                  d_ptr, d_node, d_dist, d_nh, cap, nh_bytes, use_link_metric, stream, device_index,
+                                  allow_overflow)
 
     def whatif_restore_routes(self, node_sets: Optional[Sequence[Sequence[int]]],
                               link_sets: Optional[Sequence[Sequence[int]]],
@@ -1143,30 +1098,10 @@ class SpfEngine:
         """The restore sweep resolved to routes (openr_spf_whatif_restore_routes): the return
         shape of whatif_routes. cap None: sized from a count-only pass."""
         ev, keep, n = self._restore_events(node_sets, link_sets, edge_sets, metric_sets)
-        gp, gn = _ignore_arrays(groups, len(groups))
-        gs = SpfGroups(len(groups), _p(gp), _p(gn))
-        src = np.ascontiguousarray(sources, dtype=np.uint32)
-        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
-        flags = USE_LINK_METRIC if use_link_metric else 0
-        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
-        solved = ctypes.c_uint64()
-        if cap is None:
-            _check(self._lib.openr_spf_whatif_restore_routes(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
-                                                             ctypes.byref(gs), _p(changed), None,
-                                                             ctypes.byref(solved)))
-            cap = int(changed.sum(dtype=np.uint64))
-        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
-        group = np.zeros(max(cap, 1), dtype=np.uint32)
-        metric = np.zeros(max(cap, 1), dtype=np.uint64)
-        nh = np.zeros((max(cap, 1), nb), dtype=np.uint8)
-        n_best = np.zeros(max(cap, 1), dtype=np.uint32)
-        d = WhatifRoutes(_p(ptr), _p(group), _p(metric), _p(nh), _p(n_best), cap, nb)
-        _check(self._lib.openr_spf_whatif_restore_routes(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
-                                                         ctypes.byref(gs), _p(changed), ctypes.byref(d),
-                                                         ctypes.byref(solved)))
+        out = self._event_routes(self._lib.openr_spf_whatif_restore_routes, ev, n, sources, groups, use_link_metric,
+                               cap, nh_bytes)
         del keep
-        k = int(ptr[-1])
-        return changed, ptr, group[:k], metric[:k], nh[:k], n_best[:k], int(solved.value)
+        return out
 
     def whatif_restore_routes_device(self, d_node_ptr: int, d_nodes: int, d_link_ptr: int, d_links: int,
                                      d_edge_ptr: int, d_edges: int, d_metrics: int, n_events: int, n_nodes: int,
@@ -1176,20 +1111,12 @@ class SpfEngine:
                                      nh_bytes: int, use_link_metric: bool = True, stream: int = 0,
                                      device_index: int = 0, allow_overflow: bool = False) -> Tuple[int, int]:
         """Device-pointer form: (total entries, solved); outputs as whatif_routes_device."""
-        vp = ctypes.c_void_p
-        total = ctypes.c_uint64()
-        solved = ctypes.c_uint64()
-        flags = USE_LINK_METRIC if use_link_metric else 0
-        rc = self._lib.openr_spf_whatif_restore_routes_device(
-            self._ctx, device_index, vp(d_node_ptr or None), vp(d_nodes or None), vp(d_link_ptr or None),
-            vp(d_links or None), vp(d_edge_ptr or None), vp(d_edges or None), vp(d_metrics or None), n_events, n_nodes,
-            n_links, n_edges, vp(d_sources), n_sources, flags, vp(d_group_ptr or None), vp(d_group_nodes or None),
-            n_groups, n_group_nodes, vp(d_changed), vp(d_ptr), vp(d_group or None), vp(d_metric or None),
-            vp(d_nh or None), vp(d_n_best or None), cap, nh_bytes, vp(stream or None), ctypes.byref(total),
-            ctypes.byref(solved))
-        if not (allow_overflow and rc == E2BIG):
-            _check(rc)
-        return int(total.value), int(solved.value)
+        ev = self._device_events((d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics), n_events,
+                                 n_nodes, n_links, n_edges)
+        return self._event_routes_device(self._lib.openr_spf_whatif_restore_routes_device, ev, d_sources, n_sources,
+                                         d_group_ptr, d_group_nodes, n_groups, n_group_nodes, d_changed, d_ptr,
+                                         d_group, d_metric, d_nh, d_n_best, cap, nh_bytes, use_link_metric, stream,
+                                         device_index, allow_overflow)
 
     # ---- maintenance events: overloads, link-downs and metric raises together ---------------
     def whatif_maint(self, node_sets: Optional[Sequence[Sequence[int]]], link_sets: Optional[Sequence[Sequence[int]]],
@@ -1203,27 +1130,10 @@ class SpfEngine:
         whatif_metric: (changed[n_events, n_sources] u32, ptr, node, dist, nh, solved), or
         (changed, solved) with want_delta=False. cap None: sized from a count-only pass."""
         ev, keep, n = self._restore_events(node_sets, link_sets, edge_sets, metric_sets, MaintEvents)
-        src = np.ascontiguousarray(sources, dtype=np.uint32)
-        flags = USE_LINK_METRIC if use_link_metric else 0
-        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
-        solved = ctypes.c_uint64()
-        if not want_delta or cap is None:
-            _check(self._lib.openr_spf_whatif_maint(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
-                                                    _p(changed), None, ctypes.byref(solved)))
-            if not want_delta:
-                return changed, int(solved.value)
-            cap = int(changed.sum(dtype=np.uint64))
-        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
-        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
-        node = np.zeros(max(cap, 1), dtype=np.uint32)
-        dist = np.zeros(max(cap, 1), dtype=np.uint64)
-        nh = np.zeros((max(cap, 1), nb), dtype=np.uint8)
-        d = WhatifDelta(_p(ptr), _p(node), _p(dist), _p(nh), cap, nb)
-        _check(self._lib.openr_spf_whatif_maint(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
-                                                _p(changed), ctypes.byref(d), ctypes.byref(solved)))
+        out = self._event_sweep(self._lib.openr_spf_whatif_maint, ev, n, sources, use_link_metric, want_delta, cap,
+                              nh_bytes)
         del keep
-        k = int(ptr[-1])
-        return changed, ptr, node[:k], dist[:k], nh[:k], int(solved.value)
+        return out
 
     def whatif_maint_device(self, d_node_ptr: int, d_nodes: int, d_link_ptr: int, d_links: int, d_edge_ptr: int,
                             d_edges: int, d_metrics: int, n_events: int, n_nodes: int, n_links: int, n_edges: int,
@@ -1233,19 +1143,11 @@ class SpfEngine:
         """Device-pointer form: (total entries, solved). d_link_ptr / d_edge_ptr 0: no links /
         no metric entries. d_ptr [n_units + 1] u64 CSR; unit u's entries are [ptr[u],
         ptr[u + 1]) in the kernel's order."""
-        vp = ctypes.c_void_p
-        total = ctypes.c_uint64()
-        solved = ctypes.c_uint64()
-        flags = USE_LINK_METRIC if use_link_metric else 0
-        rc = self._lib.openr_spf_whatif_maint_device(
-            self._ctx, device_index, vp(d_node_ptr or None), vp(d_nodes or None), vp(d_link_ptr or None),
-            vp(d_links or None), vp(d_edge_ptr or None), vp(d_edges or None), vp(d_metrics or None), n_events, n_nodes,
-            n_links, n_edges, vp(d_sources), n_sources, flags, vp(d_changed), vp(d_ptr), vp(d_node or None),
-            vp(d_dist or None), vp(d_nh or None), cap, nh_bytes, vp(stream or None), ctypes.byref(total),
-            ctypes.byref(solved))
-        if not (allow_overflow and rc == E2BIG):
-            _check(rc)
-        return int(total.value), int(solved.value)
+        ev = self._device_events((d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics), n_events,
+                                 n_nodes, n_links, n_edges)
+        return self._event_device(self._lib.openr_spf_whatif_maint_device, ev, d_sources, n_sources, d_changed, d_ptr,
+                                  d_node, d_dist, d_nh, cap, nh_bytes, use_link_metric, stream, device_index,
+                                  allow_overflow)
 
     def whatif_maint_routes(self, node_sets: Optional[Sequence[Sequence[int]]],
                             link_sets: Optional[Sequence[Sequence[int]]],
@@ -1256,30 +1158,10 @@ class SpfEngine:
         """The maintenance sweep resolved to routes (openr_spf_whatif_maint_routes): the return
         shape of whatif_routes. cap None: sized from a count-only pass."""
         ev, keep, n = self._restore_events(node_sets, link_sets, edge_sets, metric_sets, MaintEvents)
-        gp, gn = _ignore_arrays(groups, len(groups))
-        gs = SpfGroups(len(groups), _p(gp), _p(gn))
-        src = np.ascontiguousarray(sources, dtype=np.uint32)
-        nb = nh_bytes if nh_bytes is not None else self.nh_bytes
-        flags = USE_LINK_METRIC if use_link_metric else 0
-        changed = np.zeros((n, src.shape[0]), dtype=np.uint32)
-        solved = ctypes.c_uint64()
-        if cap is None:
-            _check(self._lib.openr_spf_whatif_maint_routes(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
-                                                           ctypes.byref(gs), _p(changed), None,
-                                                           ctypes.byref(solved)))
-            cap = int(changed.sum(dtype=np.uint64))
-        ptr = np.zeros(n * src.shape[0] + 1, dtype=np.uint64)
-        group = np.zeros(max(cap, 1), dtype=np.uint32)
-        metric = np.zeros(max(cap, 1), dtype=np.uint64)
-        nh = np.zeros((max(cap, 1), nb), dtype=np.uint8)
-        n_best = np.zeros(max(cap, 1), dtype=np.uint32)
-        d = WhatifRoutes(_p(ptr), _p(group), _p(metric), _p(nh), _p(n_best), cap, nb)
-        _check(self._lib.openr_spf_whatif_maint_routes(self._ctx, ctypes.byref(ev), _p(src), src.shape[0], flags,
-                                                       ctypes.byref(gs), _p(changed), ctypes.byref(d),
-                                                       ctypes.byref(solved)))
+        out = self._event_routes(self._lib.openr_spf_whatif_maint_routes, ev, n, sources, groups, use_link_metric,
+                               cap, nh_bytes)
         del keep
-        k = int(ptr[-1])
-        return changed, ptr, group[:k], metric[:k], nh[:k], n_best[:k], int(solved.value)
+        return out
 
     def whatif_maint_routes_device(self, d_node_ptr: int, d_nodes: int, d_link_ptr: int, d_links: int,
                                    d_edge_ptr: int, d_edges: int, d_metrics: int, n_events: int, n_nodes: int,
@@ -1289,20 +1171,12 @@ class SpfEngine:
                                    nh_bytes: int, use_link_metric: bool = True, stream: int = 0,
                                    device_index: int = 0, allow_overflow: bool = False) -> Tuple[int, int]:
         """Device-pointer form: (total entries, solved); outputs as whatif_routes_device."""
-        vp = ctypes.c_void_p
-        total = ctypes.c_uint64()
-        solved = ctypes.c_uint64()
-        flags = USE_LINK_METRIC if use_link_metric else 0
-        rc = self._lib.openr_spf_whatif_maint_routes_device(
-            self._ctx, device_index, vp(d_node_ptr or None), vp(d_nodes or None), vp(d_link_ptr or None),
-            vp(d_links or None), vp(d_edge_ptr or None), vp(d_edges or None), vp(d_metrics or None), n_events, n_nodes,
-            n_links, n_edges, vp(d_sources), n_sources, flags, vp(d_group_ptr or None), vp(d_group_nodes or None),
-            n_groups, n_group_nodes, vp(d_changed), vp(d_ptr), vp(d_group or None), vp(d_metric or None),
-            vp(d_nh or None), vp(d_n_best or None), cap, nh_bytes, vp(stream or None), ctypes.byref(total),
-            ctypes.byref(solved))
-        if not (allow_overflow and rc == E2BIG):
-            _check(rc)
-        return int(total.value), int(solved.value)
+        ev = self._device_events((d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics), n_events,
+                                 n_nodes, n_links, n_edges)
+        return self._event_routes_device(self._lib.openr_spf_whatif_maint_routes_device, ev, d_sources, n_sources,
+                                         d_group_ptr, d_group_nodes, n_groups, n_group_nodes, d_changed, d_ptr,
+                                         d_group, d_metric, d_nh, d_n_best, cap, nh_bytes, use_link_metric, stream,
+                                         device_index, allow_overflow)
 
     # ---- loop-free alternates under drain, metric, restore and maintenance events ------------
     def _event_lfa(self, fn, ev, n: int, sources, groups, use_link_metric, nh_bytes, cap, want_counts):
@@ -1374,9 +1248,7 @@ class SpfEngine:
                                 allow_overflow: bool = False) -> Tuple[int, int]:
         """Device-pointer form (openr_spf_whatif_drain_lfa_device): (total entries, solved);
         events as whatif_drain_device, outputs as whatif_lfa_device."""
-        vp = ctypes.c_void_p
-        ev = (vp(d_node_ptr or None), vp(d_nodes or None), vp(d_link_ptr or None), vp(d_links or None), n_events,
-              n_nodes, n_links)
+        ev = self._device_events((d_node_ptr, d_nodes, d_link_ptr, d_links), n_events, n_nodes, n_links)
         return self._event_lfa_device(self._lib.openr_spf_whatif_drain_lfa_device, ev, d_sources, n_sources,
                                       d_group_ptr, d_group_nodes, n_groups, n_group_nodes, d_changed, d_unprotected,
                                       d_lost_backup, d_ptr, d_group, d_metric, d_nh, d_alt, cap, nh_bytes,
@@ -1402,8 +1274,7 @@ class SpfEngine:
                                  use_link_metric: bool = True, stream: int = 0, device_index: int = 0,
                                  allow_overflow: bool = False) -> Tuple[int, int]:
         """Device-pointer form (openr_spf_whatif_metric_lfa_device): (total entries, solved)."""
-        vp = ctypes.c_void_p
-        ev = (vp(d_edge_ptr or None), vp(d_edges or None), vp(d_metrics or None), n_events, n_edges)
+        ev = self._device_events((d_edge_ptr, d_edges, d_metrics), n_events, n_edges)
         return self._event_lfa_device(self._lib.openr_spf_whatif_metric_lfa_device, ev, d_sources, n_sources,
                                       d_group_ptr, d_group_nodes, n_groups, n_group_nodes, d_changed, d_unprotected,
                                       d_lost_backup, d_ptr, d_group, d_metric, d_nh, d_alt, cap, nh_bytes,
@@ -1433,9 +1304,8 @@ class SpfEngine:
                                   nh_bytes: int = 0, use_link_metric: bool = True, stream: int = 0,
                                   device_index: int = 0, allow_overflow: bool = False) -> Tuple[int, int]:
         """Device-pointer form (openr_spf_whatif_restore_lfa_device): (total entries, solved)."""
-        vp = ctypes.c_void_p
-        ev = (vp(d_node_ptr or None), vp(d_nodes or None), vp(d_link_ptr or None), vp(d_links or None),
-              vp(d_edge_ptr or None), vp(d_edges or None), vp(d_metrics or None), n_events, n_nodes, n_links, n_edges)
+        ev = self._device_events((d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics), n_events,
+                                 n_nodes, n_links, n_edges)
         return self._event_lfa_device(self._lib.openr_spf_whatif_restore_lfa_device, ev, d_sources, n_sources,
                                       d_group_ptr, d_group_nodes, n_groups, n_group_nodes, d_changed, d_unprotected,
                                       d_lost_backup, d_ptr, d_group, d_metric, d_nh, d_alt, cap, nh_bytes,
@@ -1467,9 +1337,8 @@ class SpfEngine:
                                 device_index: int = 0, allow_overflow: bool = False) -> Tuple[int, int]:
         """Device-pointer form (openr_spf_whatif_maint_lfa_device): (total entries, solved);
         events as whatif_maint_device, outputs as whatif_lfa_device."""
-        vp = ctypes.c_void_p
-        ev = (vp(d_node_ptr or None), vp(d_nodes or None), vp(d_link_ptr or None), vp(d_links or None),
-              vp(d_edge_ptr or None), vp(d_edges or None), vp(d_metrics or None), n_events, n_nodes, n_links, n_edges)
+        ev = self._device_events((d_node_ptr, d_nodes, d_link_ptr, d_links, d_edge_ptr, d_edges, d_metrics), n_events,
+                                 n_nodes, n_links, n_edges)
         return self._event_lfa_device(self._lib.openr_spf_whatif_maint_lfa_device, ev, d_sources, n_sources,
                                       d_group_ptr, d_group_nodes, n_groups, n_group_nodes, d_changed, d_unprotected,
                                       d_lost_backup, d_ptr, d_group, d_metric, d_nh, d_alt, cap, nh_bytes,
